@@ -1,6 +1,11 @@
 """Headline benchmark: img+tokens/sec of the early-fusion VLM forward+backward step (BASELINE config 4).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  ``--full`` adds everything else the line can carry:
+board power, the step with the optimizer, the step with the fp32 tower, the matrix-pipe probe, the dominant kernel's own timing and
+the committed counter traffic, the CPU baseline and BASELINE configs 2 / 3 / 5.  ``--dump-outputs DIR`` writes what the last timed
+step handed its caller (the loss and the parameter gradients) as .npy files, for comparing two builds on identical seeded inputs.
 
 N > 1 runs one rank per GPU over RCCL.  Under ``torch.distributed.run`` (WORLD_SIZE set) this process IS a rank; started
 plainly with ``--gpus N`` it starts the N ranks itself -- a child ``python -m torch.distributed.run --nproc-per-node N bench.py ...``
@@ -260,6 +265,33 @@ class BoardPower:
                 "source": "amdgpu hwmon power1_input / freq1_input every 10 ms over the timed steps; the dense peak in `roofline` assumes 2 400 MHz"}
 
 
+def dump_outputs(out_dir, loss, named_params, budget_bytes=60 << 20):
+    """``--dump-outputs``: the loss (float64) and the gradient of every trainable parameter (float32) of the last timed step, one .npy per array,
+    plus ``grad_norms.npy`` (float64, the whole gradient's 2-norm per parameter, in the order of ``named_params``).  A gradient with more elements
+    than fit the byte budget is written as a fixed seeded sample of its elements: the same indices on every run with the same arguments."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([float(loss)], dtype=np.float64))
+    per_tensor = min(16384, budget_bytes // (4 * max(1, len(named_params))))
+    gen = torch.Generator().manual_seed(0)
+    norms = []
+    for name, p in named_params:
+        g = (p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1)
+        if g.numel() > per_tensor:
+            idx = torch.randint(0, g.numel(), (per_tensor,), generator=gen).sort().values
+            g_out = g[idx.to(g.device)]
+        else:
+            g_out = g
+        np.save(os.path.join(out_dir, f"grad.{name}.npy"), g_out.float().cpu().numpy())
+        norms.append(float(torch.linalg.vector_norm(g, dtype=torch.float64)))
+    np.save(os.path.join(out_dir, "grad_norms.npy"), np.array(norms, dtype=np.float64))
+
+
+def trainable(**modules):
+    return [(f"{prefix}.{n}", p) for prefix, m in modules.items() for n, p in m.named_parameters() if p.requires_grad]
+
+
 def launch_ranks(n):
     """``python bench.py --gpus N`` without a torchrun environment: run the N ranks as a child ``torch.distributed.run`` job (a fresh
     process tree; nothing in THIS process has initialised the GPU yet) and pass its output and exit status through."""
@@ -467,7 +499,7 @@ def run_other_config(args):
     device = torch.device("cuda", local)
     _lib.load()
     batch = args.batch if args.batch_given else spec["batch"]
-    power = BoardPower() if rank == 0 else None
+    power = BoardPower() if rank == 0 and args.full else None
     step, sync, state = _other_config_step(args.config, batch, device, rank)
 
     def fence():
@@ -495,6 +527,8 @@ def run_other_config(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t)
+    if rank == 0 and args.dump_outputs:  # each step() drops the previous gradients first: the last step's are still attached
+        dump_outputs(args.dump_outputs, loss.detach(), trainable(model=state[2]))
     if rank == 0:
         achieved = spec["flop"] * batch / (elapsed / args.steps) / 1e12
         line = {
@@ -502,12 +536,13 @@ def run_other_config(args):
             "rccl_ranks": world if world > 1 else 0, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
             "config": {"workload": spec["workload"], "per_gpu_batch": batch, "global_batch": batch * world, "parallelism": f"dp{world}", "units_per_sample": spec["units_per_sample"]},
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4), **_config_traffic(args.config, batch),
+            "roofline": {"bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+                         **(_config_traffic(args.config, batch) if args.full else {"traffic": None, "traffic_note": "not collected"}),
                          "basis": f"algorithmic {spec['flop'] / 1e9:.1f} GFLOP/sample (SURVEY 8d) x per-GPU batch / step time; device-side (HIP events) {dev_ms / args.steps:.3f} ms/step"},
-            "board_power": board_power,
+            **({"board_power": board_power} if args.full else {}),
             "loss": round(float(loss.detach()), 5), "peak_memory_gib": round(torch.cuda.max_memory_allocated(device) / 2**30, 1),
         }
-        if world == 1 and args.cpu_baseline == "auto":
+        if args.full and world == 1 and args.cpu_baseline == "auto":
             try:
                 line["cpu_baseline"] = _other_cpu_baseline(state, {2: 8, 3: 2, 5: 1}[args.config], spec["unit"])
             except Exception as exc:  # the baseline is a reported number, never the measured path
@@ -528,6 +563,10 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="per-GPU micro-batch (samples); default 160 for the headline (--config 2 / 3 / 5: 332 / 64 / 32).  Headline: 160 x 709 tokens keep 165 GiB of the 288 GB of HBM live; same-box pairs: 64 -> 34.2 / 34.1 %%, "
                     "128 -> +1.4 %%, 160 -> 35.0 / 34.9 %%, 192 -> level with 160 (202 GiB).  More rounds of tiles per launch amortise every launch's fill and tail.  (92 -- every "
                     "launch a whole number of rounds at batch ~64 -- measured the same as 64: the tail tiles of a partial round run faster, the chip is power-limited)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: board power, the legs and probes below, the dominant kernel's "
+                    "timing, the committed counter traffic, the CPU baseline and configs 2 / 3 / 5.  The switches below act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's loss and parameter gradients to DIR/*.npy "
+                    "(float64 / float32; gradients larger than the 64 MB budget as a fixed seeded sample of their elements)")
     ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
     ap.add_argument("--ragged", action="store_true", help="text lengths ~ U[256, 512] (padding mask active in attention and loss) instead of all-ones masks")
     ap.add_argument("--optimizer", choices=["on", "off"], default="on", help="also time the same steps with clip + AdamW (reported beside the fwd+bwd metric)")
@@ -545,6 +584,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.config != 4:
         return run_other_config(args)
     # MI355_DDP_REHEARSAL=1 (one-GPU boxes only): the N ranks share the visible GPUs round-robin and exchange over gloo -- every line of the N > 1 path
@@ -572,7 +613,7 @@ def main():
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
     _lib.load()
-    power = BoardPower() if rank == 0 else None
+    power = BoardPower() if rank == 0 and args.full else None
 
     vit, vit_cfg, ad, llm, llm_cfg = build_models(device)
     if args.tower != "default":
@@ -608,15 +649,19 @@ def main():
             ahead.submit(img)
         return h
 
-    def step():
+    def drop_grads():
+        llm.zero_grad(set_to_none=True)
+        ad.zero_grad(set_to_none=True)
+
+    def step(keep_grads=False):
         loss = vlm_step_loss(vit, llm, ad, img, ids, mask, hf_vit_model=False, vit_hidden=vision())
         if ahead is not None and tower_at == "backward":
             ahead.submit(img)
         sync.begin_step(embedding_tokens=ids.numel())  # the tied head / embedding bucket: dense or in two parts, by bytes (ddp.GradSync.split_pays)
         (loss * sync.loss_weight(n_targets) if (args.ragged and world > 1) else loss).backward()
         sync.finish_step()
-        llm.zero_grad(set_to_none=True)
-        ad.zero_grad(set_to_none=True)
+        if not keep_grads:
+            drop_grads()
         return loss
 
     def fence():
@@ -634,8 +679,8 @@ def main():
         power.mark()
     t0 = time.perf_counter()
     ev0.record()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(keep_grads=i == args.steps - 1)  # the last step's gradients are what --dump-outputs writes (dropped just below: host-side only)
     ev1.record()
     fence()
     elapsed = time.perf_counter() - t0
@@ -646,12 +691,15 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t)
     loss_gpu = float(loss.detach())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss_gpu, trainable(llm=llm, adapter=ad))
+    drop_grads()
 
     # The metric is forward + backward (BASELINE.json; SURVEY 8d: "optimizer step excluded (state it)").  So that nothing of a real
     # training step is left unmeasured, the same K steps are timed again WITH the optimizer: global-norm clip 1.0 + AdamW on the
     # parameter arenas (llm_quest_amd/optim.py::ArenaAdamW), reported beside `value`, never instead of it.
     train_step = None
-    if args.optimizer == "on":
+    if args.full and args.optimizer == "on":
         from llm_quest_amd.optim import ArenaAdamW
 
         opt = ArenaAdamW(list(llm.parameters()) + list(ad.parameters()), lr=1e-5, weight_decay=0.01, max_grad_norm=1.0)
@@ -685,7 +733,7 @@ def main():
     # section 4).  So that the driver's line also carries the step at the reference's precision, the same K steps are timed once more with
     # vit.tower_precision = "fp32" (split-bf16 GEMMs + exact-fp32 attention: hidden states within 1e-4 of the oracle's), reported beside `value`.
     fp32_tower = None
-    if world == 1 and tower != "fp32" and args.fp32_tower_leg == "on":
+    if args.full and world == 1 and tower != "fp32" and args.fp32_tower_leg == "on":
         vit.tower_precision = "fp32"
         for _ in range(max(args.warmup, 2)):  # (the first step still takes hidden states submitted by the bf16 tower)
             step()
@@ -727,7 +775,7 @@ def main():
                 "basis": "algorithmic 2.566 TFLOP/sample (SURVEY 8d) x per-GPU batch / step time; device-side (HIP events) "
                          f"{dev_ms / args.steps:.3f} ms/step",
             },
-            "board_power": board_power,
+            **({"board_power": board_power} if args.full else {}),
             "loss": round(loss_gpu, 5), "peak_memory_gib": round(torch.cuda.max_memory_allocated(device) / 2**30, 1),
         }
         if world > 1:  # how the N > 1 step's large NT GEMMs were launched: on the persistent kernel, or on the per-tile kernel inside a window behind a bucket group (ddp.GradSync)
@@ -738,7 +786,7 @@ def main():
             line["with_optimizer_step"] = train_step
         if fp32_tower is not None:
             line["with_fp32_tower"] = fp32_tower
-        if world == 1 and args.pipe_probe == "on":
+        if args.full and world == 1 and args.pipe_probe == "on":
             from llm_quest_amd import kernels as K_
 
             pipe = K_.mfma_pipe_rate(2.0)
@@ -749,7 +797,7 @@ def main():
                 "what_16x16x32": "the same on v_mfma_f32_16x16x32_bf16, the shape the GEMMs issue (32 products on a 128 x 64 wave tile's twelve fragments per repetition)",
                 "what": "v_mfma_f32_32x32x16_bf16 on every SIMD, random bf16 operands in registers, no memory traffic, measured on this board right after the timed steps: on random data the "
                         "board's power cap holds the pipe itself below the 2 500 TFLOP/s of `peak` (DESIGN.md section 5)"}
-        if world == 1:
+        if args.full and world == 1:
             line["roofline"]["dominant_kernel"] = {"name": "gemm_nt_persist_kernel / gemm_grouped_kernel (NT projections on the persistent form of tile 2; the block's weight gradients as one grouped launch on tile 5)", "hip_event_timing": dominant_kernel_rate(args.batch, device)}
             pmc, why_gemm = pmc_traffic()
             step_pmc, why_step = pmc_step_traffic()
@@ -769,12 +817,12 @@ def main():
                 line["roofline"]["dominant_kernel"]["over_algorithmic"] = {f: pmc[f]["over_algorithmic"] for f in pmc}
             elif pmc is None:
                 line["roofline"]["dominant_kernel"]["pmc_note"] = "withheld: " + why_gemm
-        if world == 1 and args.cpu_baseline == "auto":
+        if args.full and world == 1 and args.cpu_baseline == "auto":
             try:
                 line["cpu_baseline"] = cpu_baseline(vit, ad, llm, seed=123)
             except Exception as exc:  # the baseline is a reported number, never the measured path
                 line["cpu_baseline"] = {"value": None, "unit": "img+tok/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {exc!r}"}
-        if world == 1 and args.other_configs == "on" and not args.batch_given and not args.ragged:
+        if args.full and world == 1 and args.other_configs == "on" and not args.batch_given and not args.ragged:
             # BASELINE configs 2, 3 and 5 beside the headline (a few steps each, own processes: this one first gives its memory back), so that the driver's record
             # carries them too; `python bench.py --config N` prints each one's full line
             vit = ad = llm = img = ids = mask = ahead = sync = loss = None  # (the closures above see the same cells)
@@ -796,7 +844,7 @@ def other_configs_block(steps=5, warmup=2, budget_s=150):
 
     out = {}
     for cfg in (2, 3, 5):
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", str(cfg), "--steps", str(steps), "--warmup", str(warmup), "--cpu-baseline", "off"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", str(cfg), "--steps", str(steps), "--warmup", str(warmup), "--full", "--cpu-baseline", "off"]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=budget_s)
             d = json.loads(r.stdout.strip().splitlines()[-1])

@@ -42,7 +42,7 @@ config = sys.argv[6] if len(sys.argv) > 6 else None  # "config2" / "config3" / "
 out = {
     "kernel_sources_sha": stamp["kernel_sources_sha"], "all_sources_sha": stamp.get("all_sources_sha"), "library_sha": stamp["library_sha"], "git_sha": stamp["git_sha"],
     "per_gpu_batch": {"config2": 332, "config3": 64, "config5": 32}[config] if config else stamp["per_gpu_batch"], **({"config": config} if config else {}),
-    "note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, TCC slots) with --kernel-trace over `python3 bench.py --steps 1 --warmup 1 "
+    "note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, TCC slots) with --kernel-trace over `python3 bench.py --full --steps 1 --warmup 1 "
             "--cpu-baseline off` (per-GPU batch as stamped: 4 steps in each trace -- warm-up + timed, without and with the optimizer); figures are PER STEP = per-launch "
             "average x launches per step, so the bench's 13 stand-alone launches of each gate-up GEMM form drop out, and the optimizer's own kernels are left out (the headline step has none).  KiB units from rocprofv3; gfx950 correction: FETCH_SIZE doubled (128-byte requests "
             "tallied at 64), WRITE_SIZE exact.  Infinity-Cache hits are included in FETCH_SIZE (memory-side L2 requests).",
