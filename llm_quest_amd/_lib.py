@@ -107,6 +107,13 @@ SIGNATURES = {
     "mi355_attn_generic_dropout_fwd": [_I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _F, _F, _U, _U, _P],
     "mi355_attn_generic_dropout_bwd": [_I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _L, _P, _L, _P, _L, _P, _F, _F, _U, _U, _P],
     "mi355_attn_dropout_bwd": [_I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _L, _P, _L, _P, _L, _I, _F, _F, _U, _U, _P],
+    # hyper-connections (csrc/hyper_conn.hip)
+    "mi355_hc_width_fwd": [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _P],
+    "mi355_hc_depth_fwd": [_L, _I, _I, _P, _P, _L, _P, _P, _P],
+    "mi355_hc_depth_bwd": [_L, _I, _I, _P, _P, _P, _L, _P, _P, _P],
+    "mi355_hc_width_bwd": [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
+    "mi355_hc_stream_sum": [_L, _I, _I, _P, _P, _P],
+    "mi355_hc_stream_broadcast": [_L, _I, _I, _P, _P, _P],
 }
 # size / constant queries: no stream argument, the return value is the answer (name -> (argtypes, restype))
 QUERIES = {
@@ -116,6 +123,7 @@ QUERIES = {
     "mi355_attn_bwd_workspace_rowconst_offset": ([_I, _I, _I, _I, _I], _L),
     "mi355_attn_bwd_qnorm_partials": ([_I, _I, _I], _L),
     "mi355_embedding_bwd_sorted_workspace_bytes": ([_L, _I], _L),
+    "mi355_hc_width_bwd_partial_width": ([_I, _I], _L),
 }
 
 _lib = None
