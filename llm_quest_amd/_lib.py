@@ -114,6 +114,15 @@ SIGNATURES = {
     "mi355_hc_width_bwd": [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "mi355_hc_stream_sum": [_L, _I, _I, _P, _P, _P],
     "mi355_hc_stream_broadcast": [_L, _I, _I, _P, _P, _P],
+    # Gemma3: sliding-window attention and its row kernels (csrc/gemma3.hip)
+    "mi355_swa_attn_fwd": [_I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _F, _P],
+    "mi355_swa_attn_bwd": [_I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _L, _P, _L, _P, _L, _F, _P],
+    "mi355_g3_rmsnorm_fwd": [_L, _I, _P, _P, _P, _P, _F, _P],
+    "mi355_g3_rmsnorm_bwd": [_L, _I, _P, _P, _P, _P, _P, _P, _I, _F, _P],
+    "mi355_g3_rope_ln_fwd": [_L, _I, _I, _I, _I, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _L, _F, _P],
+    "mi355_g3_rope_ln_bwd": [_L, _I, _I, _I, _I, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, _L, _P, _I, _F, _P],
+    "mi355_geglu_fwd": [_L, _I, _P, _P, _P],
+    "mi355_geglu_bwd": [_L, _I, _P, _P, _P, _P],
 }
 # size / constant queries: no stream argument, the return value is the answer (name -> (argtypes, restype))
 QUERIES = {

@@ -16,6 +16,7 @@ from .rope import RoPE
 class GlobalBuffers:
     _mask_buffer = {}
     _rope_buffer = {}
+    _swa_buffer = {}  # both sliding-window tables share it upstream; here each kind has its own key
 
     @staticmethod
     def get_causal_mask(ctx_len):
@@ -35,3 +36,28 @@ class GlobalBuffers:
                 base=rope_base, head_dim=head_dim, ctx_len=ctx_len, smooth_scaling_cfg=smooth_scaling_cfg, rotation_factor=rotation_factor
             )
         return GlobalBuffers._rope_buffer[key]
+
+    @staticmethod
+    def get_swa_buffers(ctx_len, window_size):
+        """bool (ctx, window), True = masked: slot k of query i's window holds key i - (window - 1) + k, which lies before the sequence start
+        iff k < window - 1 - i (buffers.py:57-68, the mask of Gemma3's window gather).  The HIP kernels never read it."""
+        key = ("gather", ctx_len, window_size, str(torch.get_default_device()))
+        m = GlobalBuffers._swa_buffer.get(key)
+        if m is None:
+            slot = torch.arange(window_size).unsqueeze(0)
+            query = torch.arange(ctx_len).unsqueeze(1)
+            m = slot < (window_size - 1 - query)
+            GlobalBuffers._swa_buffer[key] = m
+        return m
+
+    @staticmethod
+    def get_swa_mask(ctx_len, window_size):
+        """bool (ctx, ctx), True = masked: key j is hidden from query i iff j > i or j <= i - window (buffers.py:71-87)."""
+        key = ("band", ctx_len, window_size, str(torch.get_default_device()))
+        m = GlobalBuffers._swa_buffer.get(key)
+        if m is None:
+            query = torch.arange(ctx_len).unsqueeze(1)
+            k = torch.arange(ctx_len).unsqueeze(0)
+            m = (k > query) | (k <= query - window_size)
+            GlobalBuffers._swa_buffer[key] = m
+        return m

@@ -1,0 +1,719 @@
+// Gemma3 (reference llama3_to_gemma3/): sliding-window causal attention and the three row kernels the family needs beside what exists.
+//
+// Sliding-window attention (gemma3_attention.py:49-128, where it is a [b, h, s, w, d] gather of key / value windows):
+//   allowed(i, j) = i - W < j <= i,  W >= 1;  softmax over the allowed keys of scale * q_i . k_j;  W >= S is plain causal attention.
+// Same data flow as attention_generic.hip -- S^T = K Q^T with the query on the MFMA lane (mfma_f32_32x32x16_bf16), lane-local online softmax,
+// P^T packed from the accumulators as the B operand of O^T += V^T P^T, plain padded LDS images, one 32-key tile per barrier pair, no
+// pipelining; backward with delta = rowsum(dO * O), a query-major dQ pass and a key-major dK/dV pass, no atomics -- and one difference, which
+// is the point: only the key tiles that meet the band are walked.  A workgroup of 128 queries starting at qb visits keys
+// max(0, qb - W + 1) .. q_last; a workgroup of 128 keys [kb, k_last] visits queries kb .. min(S - 1, k_last + W - 1); inside it a wave skips
+// the tiles outside its own 32 rows' band.  No row is ever fully masked (j = i is always allowed).  The host clamps W to S, so every W >= S runs
+// the same instructions on the same numbers.
+//
+// Row kernels (one wave per row, fp32 math, one rounding at the output; parameter gradients as per-workgroup partial rows for
+// mi355_reduce_rows_f32):
+//   Gemma RMSNorm (gemma3_transformer_block.py:14-37): y = scale * x / (sqrt(mean(x^2)) + eps) -- eps is added to the RMS, not under the root.
+//   RoPE + per-head LayerNorm (gemma3_attention.py:203-207, 13-43): half-split rotation with bf16-rounded cos / sin, then
+//     (r - mean) / (std + eps) * scale + shift over head_dim, population std; one scale / shift pair for the query heads, one for the key heads.
+//   GeGLU (gemma3_transformer_block.py:101-106): a = lin1 * gelu_erf(lin_gate) on the fused [T, 2F] projection.
+#include <initializer_list>
+
+#include "common.h"
+
+namespace {
+
+constexpr float LOG2E = 1.4426950408889634f;
+constexpr float LN2 = 0.6931471805599453f;
+#define NEG_INF (-__builtin_huge_valf())
+
+template <int D>
+struct SW {
+    static constexpr int PITCH = D * 2 + 16;  // bytes per LDS row
+    static constexpr int KS = D / 16;         // k-steps over d
+    static constexpr int DT = D / 32;         // 32-row tiles of a transposed [d x 32] accumulator
+    static constexpr int IMG = 32 * PITCH;    // one 32-row image
+};
+
+// cooperative load of 32 rows x D bf16 into a padded LDS image; rows >= rows_valid are zero
+template <int D>
+__device__ __forceinline__ void load_tile(char* img, const bf16_t* base, int64_t ld, int rows_valid, int tid) {
+    constexpr int CH = D / 8;
+    for (int c = tid; c < 32 * CH; c += 256) {
+        const int row = c / CH, ch = c % CH;
+        u32x4 v = {0, 0, 0, 0};
+        if (row < rows_valid) v = *reinterpret_cast<const u32x4*>(base + (int64_t)row * ld + ch * 8);
+        *reinterpret_cast<u32x4*>(img + row * SW<D>::PITCH + ch * 16) = v;
+    }
+}
+// A operand (32 rows x 16 k) from a row image: row = lane & 31, k = 16 ks + 8 (lane >> 5) ..
+template <int D>
+__device__ __forceinline__ bf16x8 frag_rows(const char* img, int ks, int lane) {
+    return *reinterpret_cast<const bf16x8*>(img + (lane & 31) * SW<D>::PITCH + (2 * ks + (lane >> 5)) * 16);
+}
+// A operand of the TRANSPOSE of a row image: rows of A = image columns c0 .. c0+31, k = image rows in the order in which an accumulator tile
+// packs into a B operand: element j <-> image row k0 + 8 (j >> 2) + 4 (lane >> 5) + (j & 3)
+template <int D>
+__device__ __forceinline__ bf16x8 frag_cols(const char* img, int c0, int k0, int lane) {
+    const int g = lane >> 4, q4 = (lane >> 2) & 3, p = lane & 3;
+    const int row = k0 + 4 * (g >> 1) + q4;
+    const int col = c0 + 16 * (g & 1) + 4 * p;
+    const char* a = img + row * SW<D>::PITCH + col * 2;
+    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(a));
+    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(a + 8 * SW<D>::PITCH));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+__device__ __forceinline__ bf16x8 pack_frag(const f32x16& x, int s) {
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = pack_bf2(x[8 * s + 2 * e], x[8 * s + 2 * e + 1]);
+    return __builtin_bit_cast(bf16x8, o);
+}
+// B operand fragments of a row held on the lane (row = lane & 31 of the wave's 32 rows)
+template <int D>
+__device__ __forceinline__ void load_row_frags(const bf16_t* rowptr, bool valid, int lane, bf16x8 (&f)[SW<D>::KS]) {
+#pragma unroll
+    for (int ks = 0; ks < SW<D>::KS; ++ks) {
+        u32x4 v = {0, 0, 0, 0};
+        if (valid) v = *reinterpret_cast<const u32x4*>(rowptr + 16 * ks + 8 * (lane >> 5));
+        f[ks] = __builtin_bit_cast(bf16x8, v);
+    }
+}
+// accumulator tile [32 d x 32 rows-on-lane] -> token-major bf16 rows (4 consecutive d per 8-byte store)
+template <int NDT>
+__device__ __forceinline__ void store_t_tiles(const f32x16 (&acc)[NDT], float mul, bf16_t* rowptr, bool valid, int lane) {
+    if (!valid) return;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+        for (int i4 = 0; i4 < 4; ++i4) {
+            u32x2 w;
+            w[0] = pack_bf2(acc[dt][4 * i4] * mul, acc[dt][4 * i4 + 1] * mul);
+            w[1] = pack_bf2(acc[dt][4 * i4 + 2] * mul, acc[dt][4 * i4 + 3] * mul);
+            *reinterpret_cast<u32x2*>(rowptr + 32 * dt + 8 * i4 + 4 * (lane >> 5)) = w;
+        }
+}
+
+// ------------------------------------------------------------------------------------------------ sliding-window attention, forward
+// W is already clamped to [1, S] and S <= 2^30 - 64 (check_swa): every sum of an index and W below stays inside int.
+template <int D>
+__global__ __launch_bounds__(256) void swa_fwd_kernel(int S, int Hq, int Hkv, int W, const bf16_t* __restrict__ q, int64_t ldq,
+                                                      const bf16_t* __restrict__ k, int64_t ldk, const bf16_t* __restrict__ v, int64_t ldv,
+                                                      bf16_t* __restrict__ o, int64_t ldo, float* __restrict__ lse, float scale_log2) {
+    using C = SW<D>;
+    __shared__ __attribute__((aligned(16))) char smem[2 * C::IMG];
+    char* kimg = smem;
+    char* vimg = smem + C::IMG;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.z, h = blockIdx.y, hkv = h / (Hq / Hkv);
+    const int qb = blockIdx.x * 128;
+    const int q0 = qb + wave * 32;
+    const int query = q0 + (lane & 31);
+    const bool qvalid = query < S;
+    const int64_t tok0 = (int64_t)b * S;
+    bf16x8 qf[C::KS];
+    load_row_frags<D>(q + (tok0 + query) * ldq + (int64_t)h * D, qvalid, lane, qf);
+    f32x16 acc[C::DT];
+#pragma unroll
+    for (int dt = 0; dt < C::DT; ++dt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[dt][i] = 0.f;
+    float m = NEG_INF, l = 0.f;
+    const int qlast = (qb + 127 < S ? qb + 127 : S - 1);
+    const int kfirst = qb - W + 1 > 0 ? qb - W + 1 : 0;  // first key of the workgroup's first query's window
+    for (int kt = kfirst / 32; kt <= qlast / 32; ++kt) {
+        const int key0 = kt * 32;
+        __syncthreads();
+        load_tile<D>(kimg, k + (tok0 + key0) * ldk + (int64_t)hkv * D, ldk, S - key0, threadIdx.x);
+        load_tile<D>(vimg, v + (tok0 + key0) * ldv + (int64_t)hkv * D, ldv, S - key0, threadIdx.x);
+        __syncthreads();
+        // tile above this wave's diagonal, or wholly before the window of its first query (later queries' windows start later still)
+        if (q0 >= S || key0 > q0 + 31 || key0 + 31 + W <= q0) continue;
+        f32x16 s;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[i] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < C::KS; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(kimg, ks, lane), qf[ks], s, 0, 0, 0);
+        float mx = NEG_INF;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int key = key0 + 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3);
+            const bool ok = key < S && key <= query && key + W > query;
+            s[i] = ok ? s[i] * scale_log2 : NEG_INF;
+            mx = fmaxf(mx, s[i]);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m, mx);
+        const float m_use = m_new == NEG_INF ? 0.f : m_new;  // a row whose window this tile does not reach yet
+        const float alpha = exp2f(m - m_use);
+        float rs = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            s[i] = exp2f(s[i] - m_use);
+            rs += s[i];
+        }
+        rs += __shfl_xor(rs, 32, 64);
+        l = l * alpha + rs;
+        m = m_new;
+#pragma unroll
+        for (int dt = 0; dt < C::DT; ++dt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[dt][i] *= alpha;
+        const bf16x8 p0 = pack_frag(s, 0), p1 = pack_frag(s, 1);
+#pragma unroll
+        for (int dt = 0; dt < C::DT; ++dt) {
+            acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(vimg, 32 * dt, 0, lane), p0, acc[dt], 0, 0, 0);
+            acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(vimg, 32 * dt, 16, lane), p1, acc[dt], 0, 0, 0);
+        }
+    }
+    store_t_tiles<C::DT>(acc, 1.f / l, o + (tok0 + query) * ldo + (int64_t)h * D, qvalid, lane);
+    if (lane < 32 && qvalid) lse[((int64_t)b * Hq + h) * S + query] = (m + log2f(l)) * LN2;
+}
+
+// delta[b, h, s] = sum_d dO * O
+__global__ __launch_bounds__(256) void swa_delta_kernel(int64_t tokens, int S, int Hq, int D, const bf16_t* __restrict__ o, int64_t ldo,
+                                                        const bf16_t* __restrict__ d_o, int64_t lddo, float* __restrict__ delta) {
+    const int lane = threadIdx.x & 63;
+    const int64_t total = tokens * Hq;
+    for (int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); item < total; item += (int64_t)gridDim.x * 4) {
+        const int64_t t = item / Hq;
+        const int h = (int)(item % Hq);
+        float acc = 0.f;
+        for (int i = lane; i < D; i += 64) acc += bf2f(o[t * ldo + (int64_t)h * D + i]) * bf2f(d_o[t * lddo + (int64_t)h * D + i]);
+        acc = wave_sum(acc);
+        if (lane == 0) delta[((t / S) * Hq + h) * S + (t % S)] = acc;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ dQ pass (query-major, the forward's band)
+template <int D>
+__global__ __launch_bounds__(256) void swa_bwd_dq_kernel(int S, int Hq, int Hkv, int W, const bf16_t* __restrict__ q, int64_t ldq,
+                                                         const bf16_t* __restrict__ k, int64_t ldk, const bf16_t* __restrict__ v, int64_t ldv,
+                                                         const bf16_t* __restrict__ d_o, int64_t lddo, const float* __restrict__ lse,
+                                                         const float* __restrict__ delta, bf16_t* __restrict__ dq, int64_t lddq, float scale) {
+    using C = SW<D>;
+    __shared__ __attribute__((aligned(16))) char smem[2 * C::IMG];
+    char* kimg = smem;
+    char* vimg = smem + C::IMG;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.z, h = blockIdx.y, hkv = h / (Hq / Hkv);
+    const int qb = blockIdx.x * 128;
+    const int q0 = qb + wave * 32;
+    const int query = q0 + (lane & 31);
+    const bool qvalid = query < S;
+    const int64_t tok0 = (int64_t)b * S;
+    bf16x8 qf[C::KS], gf[C::KS];
+    load_row_frags<D>(q + (tok0 + query) * ldq + (int64_t)h * D, qvalid, lane, qf);
+    load_row_frags<D>(d_o + (tok0 + query) * lddo + (int64_t)h * D, qvalid, lane, gf);
+    const float lse_q = qvalid ? lse[((int64_t)b * Hq + h) * S + query] * LOG2E : 0.f;
+    const float delta_q = qvalid ? delta[((int64_t)b * Hq + h) * S + query] : 0.f;
+    const float scale_log2 = scale * LOG2E;
+    f32x16 acc[C::DT];
+#pragma unroll
+    for (int dt = 0; dt < C::DT; ++dt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[dt][i] = 0.f;
+    const int qlast = (qb + 127 < S ? qb + 127 : S - 1);
+    const int kfirst = qb - W + 1 > 0 ? qb - W + 1 : 0;
+    for (int kt = kfirst / 32; kt <= qlast / 32; ++kt) {
+        const int key0 = kt * 32;
+        __syncthreads();
+        load_tile<D>(kimg, k + (tok0 + key0) * ldk + (int64_t)hkv * D, ldk, S - key0, threadIdx.x);
+        load_tile<D>(vimg, v + (tok0 + key0) * ldv + (int64_t)hkv * D, ldv, S - key0, threadIdx.x);
+        __syncthreads();
+        if (q0 >= S || key0 > q0 + 31 || key0 + 31 + W <= q0) continue;
+        f32x16 s, dp;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < C::KS; ++ks) {
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(kimg, ks, lane), qf[ks], s, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(vimg, ks, lane), gf[ks], dp, 0, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int key = key0 + 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3);
+            const bool ok = qvalid && key <= query && key + W > query;
+            const float p = ok ? exp2f(s[i] * scale_log2 - lse_q) : 0.f;
+            s[i] = p * (dp[i] - delta_q) * scale;
+        }
+        const bf16x8 d0 = pack_frag(s, 0), d1 = pack_frag(s, 1);
+#pragma unroll
+        for (int dt = 0; dt < C::DT; ++dt) {
+            acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(kimg, 32 * dt, 0, lane), d0, acc[dt], 0, 0, 0);
+            acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(kimg, 32 * dt, 16, lane), d1, acc[dt], 0, 0, 0);
+        }
+    }
+    store_t_tiles<C::DT>(acc, 1.f, dq + (tok0 + query) * lddq + (int64_t)h * D, qvalid, lane);
+}
+
+// ------------------------------------------------------------------------------------------------ dK/dV pass (key-major)
+// A wave owns 32 keys of one kv head; all q heads of the group and the query tiles kb .. min(S - 1, k_last + W - 1) are walked.
+template <int D>
+__global__ __launch_bounds__(256) void swa_bwd_dkv_kernel(int S, int Hq, int Hkv, int W, const bf16_t* __restrict__ q, int64_t ldq,
+                                                          const bf16_t* __restrict__ k, int64_t ldk, const bf16_t* __restrict__ v, int64_t ldv,
+                                                          const bf16_t* __restrict__ d_o, int64_t lddo, const float* __restrict__ lse,
+                                                          const float* __restrict__ delta, bf16_t* __restrict__ dk, int64_t lddk,
+                                                          bf16_t* __restrict__ dv, int64_t lddv, float scale) {
+    using C = SW<D>;
+    constexpr int NDT = C::DT;
+    __shared__ __attribute__((aligned(16))) char smem[2 * C::IMG];
+    __shared__ float stat[2][32];
+    char* qimg = smem;
+    char* gimg = smem + C::IMG;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.z, hkv = blockIdx.y, rep = Hq / Hkv;
+    const int kb = blockIdx.x * 128;
+    const int k0 = kb + wave * 32;
+    const int key = k0 + (lane & 31);
+    const bool kvalid = key < S;
+    const int64_t tok0 = (int64_t)b * S;
+    bf16x8 kf[C::KS], vf[C::KS];
+    load_row_frags<D>(k + (tok0 + key) * ldk + (int64_t)hkv * D, kvalid, lane, kf);
+    load_row_frags<D>(v + (tok0 + key) * ldv + (int64_t)hkv * D, kvalid, lane, vf);
+    const float scale_log2 = scale * LOG2E;
+    f32x16 adk[NDT], adv[NDT];
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) adk[dt][i] = adv[dt][i] = 0.f;
+    const int klast = (kb + 127 < S ? kb + 127 : S - 1);
+    const int qend = (klast + W - 1 < S - 1 ? klast + W - 1 : S - 1);  // last query that sees a key of this workgroup
+    for (int hq = hkv * rep; hq < (hkv + 1) * rep; ++hq) {
+        for (int qt = kb / 32; qt <= qend / 32; ++qt) {
+            const int qs = qt * 32;
+            __syncthreads();
+            load_tile<D>(qimg, q + (tok0 + qs) * ldq + (int64_t)hq * D, ldq, S - qs, threadIdx.x);
+            load_tile<D>(gimg, d_o + (tok0 + qs) * lddo + (int64_t)hq * D, lddo, S - qs, threadIdx.x);
+            if (threadIdx.x < 32) {
+                const bool okq = qs + threadIdx.x < S;
+                stat[0][threadIdx.x] = okq ? lse[((int64_t)b * Hq + hq) * S + qs + threadIdx.x] * LOG2E : 0.f;
+                stat[1][threadIdx.x] = okq ? delta[((int64_t)b * Hq + hq) * S + qs + threadIdx.x] : 0.f;
+            }
+            __syncthreads();
+            // every query of the tile precedes this wave's keys, or the tile starts past the window of its last key
+            if (k0 >= S || qs + 31 < k0 || qs >= k0 + 31 + W) continue;
+            f32x16 s, dp;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
+#pragma unroll
+            for (int ks = 0; ks < C::KS; ++ks) {
+                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(qimg, ks, lane), kf[ks], s, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(gimg, ks, lane), vf[ks], dp, 0, 0, 0);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int r = 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3);
+                const int qi = qs + r;
+                const bool ok = kvalid && qi < S && key <= qi && key + W > qi;
+                const float p = ok ? exp2f(s[i] * scale_log2 - stat[0][r]) : 0.f;
+                s[i] = p;
+                dp[i] = p * (dp[i] - stat[1][r]) * scale;
+            }
+            const bf16x8 p0 = pack_frag(s, 0), p1 = pack_frag(s, 1), d0 = pack_frag(dp, 0), d1 = pack_frag(dp, 1);
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt) {
+                adv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(gimg, 32 * dt, 0, lane), p0, adv[dt], 0, 0, 0);
+                adv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(gimg, 32 * dt, 16, lane), p1, adv[dt], 0, 0, 0);
+                adk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(qimg, 32 * dt, 0, lane), d0, adk[dt], 0, 0, 0);
+                adk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(qimg, 32 * dt, 16, lane), d1, adk[dt], 0, 0, 0);
+            }
+        }
+    }
+    store_t_tiles<NDT>(adk, 1.f, dk + (tok0 + key) * lddk + (int64_t)hkv * D, kvalid, lane);
+    store_t_tiles<NDT>(adv, 1.f, dv + (tok0 + key) * lddv + (int64_t)hkv * D, kvalid, lane);
+}
+
+// the kernels move 16 bytes at a time: every operand pointer must be 16-byte aligned (NULL passes here and is refused by the null check)
+bool aligned16(std::initializer_list<const void*> ps) {
+    for (const void* p : ps)
+        if ((uintptr_t)p & 15) return false;
+    return true;
+}
+
+int check_swa(const char* who, int B, int S, int Hq, int Hkv, int D, int W, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo) {
+    MI355_REQUIRE(B >= 0 && S >= 0, "%s: negative batch or sequence length", who);
+    MI355_REQUIRE(W >= 1, "%s: window %d must be at least 1", who, W);
+    MI355_REQUIRE(Hq > 0 && Hkv > 0 && Hq % Hkv == 0, "%s: query heads (%d) must be a multiple of kv heads (%d)", who, Hq, Hkv);
+    MI355_REQUIRE(D == 32 || D == 64 || D == 128, "%s: head_dim %d not built (32, 64, 128)", who, D);
+    MI355_REQUIRE(ldq >= (int64_t)Hq * D && ldo >= (int64_t)Hq * D && ldk >= (int64_t)Hkv * D && ldv >= (int64_t)Hkv * D,
+                  "%s: leading dimension smaller than heads*head_dim", who);
+    MI355_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0, "%s: leading dimensions must be multiples of 8 elements", who);
+    // S <= 2^30 - 64: with W clamped to S the largest index sum in the kernels, k0 + 31 + W < 2 S + 32, stays inside int
+    MI355_REQUIRE(B <= 65535 && Hq <= 65535 && S <= (1 << 30) - 64, "%s: grid limits (B, Hq <= 65535, S <= 2^30 - 64)", who);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ row helpers
+__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        f[2 * e] = __uint_as_float(v[e] << 16);
+        f[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u);
+    }
+}
+__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = pack_bf2(f[2 * e], f[2 * e + 1]);
+    return o;
+}
+__device__ __forceinline__ float rbf(float x) { return bf2f(f2bf(x)); }
+
+inline int row_grid(int64_t rows) {
+    int64_t g = (rows + 3) / 4;
+    return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+}
+
+// ------------------------------------------------------------------------------------------------ Gemma RMSNorm
+__global__ __launch_bounds__(256) void g3_rmsnorm_fwd_kernel(int64_t rows, int width, const bf16_t* __restrict__ x, const bf16_t* __restrict__ res,
+                                                             const bf16_t* __restrict__ w, bf16_t* __restrict__ y, float eps) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nvec = width >> 3;
+    for (int64_t row = (int64_t)blockIdx.x * 4 + wv; row < rows; row += (int64_t)gridDim.x * 4) {
+        float ss = 0.f;
+        for (int i = lane; i < nvec; i += 64) {
+            float xv[8];
+            unpack8(*reinterpret_cast<const u32x4*>(x + row * width + i * 8), xv);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ss += xv[e] * xv[e];
+        }
+        const float a = 1.0f / (sqrtf(wave_sum(ss) / (float)width) + eps);
+        for (int i = lane; i < nvec; i += 64) {
+            float xv[8], wf[8], o[8], rs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            unpack8(*reinterpret_cast<const u32x4*>(x + row * width + i * 8), xv);
+            unpack8(*reinterpret_cast<const u32x4*>(w + i * 8), wf);
+            if (res) unpack8(*reinterpret_cast<const u32x4*>(res + row * width + i * 8), rs);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = wf[e] * (xv[e] * a) + rs[e];
+            *reinterpret_cast<u32x4*>(y + row * width + i * 8) = pack8(o);
+        }
+    }
+}
+
+// y = w x a, a = 1 / (r + eps), r = sqrt(mean x^2):  dx = a g - a^2 x <g, x> / (width r), g = w dy  (the second term is 0 for an all-zero row:
+// |x| / r is bounded and <g, x> = 0);  dw = sum over rows of dy x a.
+__global__ __launch_bounds__(256) void g3_rmsnorm_bwd_kernel(int64_t rows, int width, const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
+                                                             const bf16_t* __restrict__ dy, const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx,
+                                                             float* __restrict__ dw_partial, float eps) {
+    extern __shared__ __attribute__((aligned(16))) float g3_dw_lds[];  // [4][width]: one region per wave, summed in a fixed order
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nvec = width >> 3;
+    float* dw_mine = g3_dw_lds + wv * width;  // element i*8+e is touched by lane i % 64 of this wave only: plain adds
+    for (int i = threadIdx.x; i < 4 * width; i += 256) g3_dw_lds[i] = 0.f;
+    __syncthreads();
+    for (int64_t row = (int64_t)blockIdx.x * 4 + wv; row < rows; row += (int64_t)gridDim.x * 4) {
+        float ss = 0.f, dot = 0.f;
+        for (int i = lane; i < nvec; i += 64) {
+            float xv[8], dyv[8], wf[8];
+            unpack8(*reinterpret_cast<const u32x4*>(x + row * width + i * 8), xv);
+            unpack8(*reinterpret_cast<const u32x4*>(dy + row * width + i * 8), dyv);
+            unpack8(*reinterpret_cast<const u32x4*>(w + i * 8), wf);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                ss += xv[e] * xv[e];
+                dot += dyv[e] * wf[e] * xv[e];
+            }
+        }
+        const float r = sqrtf(wave_sum(ss) / (float)width);
+        const float a = 1.0f / (r + eps);
+        dot = wave_sum(dot);
+        const float coef = r > 0.f ? a * a * dot / ((float)width * r) : 0.f;
+        for (int i = lane; i < nvec; i += 64) {
+            float xv[8], dyv[8], wf[8], o[8], rs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            unpack8(*reinterpret_cast<const u32x4*>(x + row * width + i * 8), xv);
+            unpack8(*reinterpret_cast<const u32x4*>(dy + row * width + i * 8), dyv);
+            unpack8(*reinterpret_cast<const u32x4*>(w + i * 8), wf);
+            if (dres) unpack8(*reinterpret_cast<const u32x4*>(dres + row * width + i * 8), rs);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                o[e] = a * dyv[e] * wf[e] - coef * xv[e] + rs[e];
+                dw_mine[i * 8 + e] += dyv[e] * xv[e] * a;
+            }
+            *reinterpret_cast<u32x4*>(dx + row * width + i * 8) = pack8(o);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < width; i += 256)
+        dw_partial[(int64_t)blockIdx.x * width + i] = ((g3_dw_lds[i] + g3_dw_lds[width + i]) + g3_dw_lds[2 * width + i]) + g3_dw_lds[3 * width + i];
+}
+
+// ------------------------------------------------------------------------------------------------ RoPE + per-head LayerNorm
+// A row is one (token, head), head < Hq a query head, else a key head; a lane owns feature j of the first half and its partner j + D/2, so a wave
+// covers 128 / D rows at a time and the row sums are shuffles among the D/2 lanes of a row.
+template <int HALF>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+    for (int o = HALF / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int D, bool BWD>
+__global__ __launch_bounds__(256) void g3_rope_ln_kernel(int64_t tokens, int S, int Hq, int Hkv, const bf16_t* __restrict__ x, int64_t ldx,
+                                                         const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+                                                         const bf16_t* __restrict__ q_scale, const bf16_t* __restrict__ q_shift,
+                                                         const bf16_t* __restrict__ k_scale, const bf16_t* __restrict__ k_shift,
+                                                         const bf16_t* __restrict__ dy, int64_t lddy, bf16_t* __restrict__ out, int64_t ldo,
+                                                         float* __restrict__ partial, float eps) {
+    constexpr int HALF = D / 2, RPW = 64 / HALF;
+    __shared__ float acc_lds[4][RPW][4][D];  // [wave][row of the wave][q scale, q shift, k scale, k shift][feature]
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int sub = lane / HALF, j = lane % HALF;
+    const int H = Hq + Hkv;
+    const int64_t total = tokens * H;
+    const int64_t groups = (total + RPW - 1) / RPW;
+    const float qs1 = bf2f(q_scale[j]), qs2 = bf2f(q_scale[j + HALF]), ks1 = bf2f(k_scale[j]), ks2 = bf2f(k_scale[j + HALF]);
+    const float qb1 = bf2f(q_shift[j]), qb2 = bf2f(q_shift[j + HALF]), kb1 = bf2f(k_shift[j]), kb2 = bf2f(k_shift[j + HALF]);
+    float g_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // q scale (j, j+HALF), q shift, k scale, k shift
+    for (int64_t g = (int64_t)blockIdx.x * 4 + wv; g < groups; g += (int64_t)gridDim.x * 4) {
+        const int64_t row = g * RPW + sub;
+        const bool valid = row < total;
+        const int64_t t = valid ? row / H : 0;
+        const int h = valid ? (int)(row % H) : 0;
+        const bool is_q = h < Hq;
+        const int pos = (int)(t % S);
+        float x1 = 0.f, x2 = 0.f;
+        if (valid) {
+            x1 = bf2f(x[t * ldx + (int64_t)h * D + j]);
+            x2 = bf2f(x[t * ldx + (int64_t)h * D + j + HALF]);
+        }
+        const float c1 = rbf(cos_t[(int64_t)pos * D + j]), c2 = rbf(cos_t[(int64_t)pos * D + j + HALF]);
+        const float s1 = rbf(sin_t[(int64_t)pos * D + j]), s2 = rbf(sin_t[(int64_t)pos * D + j + HALF]);
+        const float r1 = c1 * x1 - s1 * x2, r2 = c2 * x2 + s2 * x1;  // cos * x + sin * cat(-x2, x1)
+        const float mu = group_sum<HALF>(r1 + r2) / (float)D;
+        const float e1 = r1 - mu, e2 = r2 - mu;
+        const float sd = sqrtf(group_sum<HALF>(e1 * e1 + e2 * e2) / (float)D);
+        const float a = 1.0f / (sd + eps);
+        const float sc1 = is_q ? qs1 : ks1, sc2 = is_q ? qs2 : ks2;
+        if (!BWD) {
+            if (valid) {
+                out[t * ldo + (int64_t)h * D + j] = f2bf(e1 * a * sc1 + (is_q ? qb1 : kb1));
+                out[t * ldo + (int64_t)h * D + j + HALF] = f2bf(e2 * a * sc2 + (is_q ? qb2 : kb2));
+            }
+        } else {
+            float d1 = 0.f, d2 = 0.f;
+            if (valid) {
+                d1 = bf2f(dy[t * lddy + (int64_t)h * D + j]);
+                d2 = bf2f(dy[t * lddy + (int64_t)h * D + j + HALF]);
+            }
+            const float g1 = d1 * sc1, g2 = d2 * sc2;
+            const float mg = group_sum<HALF>(g1 + g2) / (float)D;
+            const float gd = group_sum<HALF>(g1 * e1 + g2 * e2);
+            const float coef = sd > 0.f ? a * a * gd / ((float)D * sd) : 0.f;
+            const float dr1 = a * (g1 - mg) - coef * e1, dr2 = a * (g2 - mg) - coef * e2;
+            if (valid) {  // the adjoint of the rotation: dx = cos * dr + (z2, -z1), z = sin * dr
+                out[t * ldo + (int64_t)h * D + j] = f2bf(c1 * dr1 + s2 * dr2);
+                out[t * ldo + (int64_t)h * D + j + HALF] = f2bf(c2 * dr2 - s1 * dr1);
+                const int o = is_q ? 0 : 4;
+                g_acc[o] += d1 * e1 * a;
+                g_acc[o + 1] += d2 * e2 * a;
+                g_acc[o + 2] += d1;
+                g_acc[o + 3] += d2;
+            }
+        }
+    }
+    if (BWD) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            acc_lds[wv][sub][c][j] = g_acc[2 * c];
+            acc_lds[wv][sub][c][j + HALF] = g_acc[2 * c + 1];
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < 4 * D; i += 256) {
+            float s = 0.f;
+            for (int w = 0; w < 4; ++w)
+                for (int r = 0; r < RPW; ++r) s += acc_lds[w][r][i / D][i % D];
+            partial[(int64_t)blockIdx.x * 4 * D + i] = s;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ GeGLU
+// gelu(g) = g Phi(g) with Phi(g) = erfc(-g / sqrt 2) / 2: no cancellation in the left tail
+__device__ __forceinline__ float norm_cdf(float g) { return 0.5f * erfcf(-g * 0.70710678118654752440f); }
+
+__global__ __launch_bounds__(256) void g3_geglu_fwd_kernel(int64_t tokens, int F, const bf16_t* __restrict__ gu, bf16_t* __restrict__ a) {
+    const int fv = F >> 3;
+    const int64_t total = tokens * fv;
+    for (int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x; item < total; item += (int64_t)gridDim.x * 256) {
+        const int64_t t = item / fv;
+        const int c = (int)(item % fv) * 8;
+        float u[8], g[8], o[8];
+        unpack8(*reinterpret_cast<const u32x4*>(gu + t * 2 * F + c), u);
+        unpack8(*reinterpret_cast<const u32x4*>(gu + t * 2 * F + F + c), g);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = u[e] * g[e] * norm_cdf(g[e]);
+        *reinterpret_cast<u32x4*>(a + t * F + c) = pack8(o);
+    }
+}
+
+__global__ __launch_bounds__(256) void g3_geglu_bwd_kernel(int64_t tokens, int F, const bf16_t* __restrict__ gu, const bf16_t* __restrict__ da,
+                                                           bf16_t* __restrict__ dgu) {
+    const int fv = F >> 3;
+    const int64_t total = tokens * fv;
+    for (int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x; item < total; item += (int64_t)gridDim.x * 256) {
+        const int64_t t = item / fv;
+        const int c = (int)(item % fv) * 8;
+        float u[8], g[8], d[8], du[8], dg[8];
+        unpack8(*reinterpret_cast<const u32x4*>(gu + t * 2 * F + c), u);
+        unpack8(*reinterpret_cast<const u32x4*>(gu + t * 2 * F + F + c), g);
+        unpack8(*reinterpret_cast<const u32x4*>(da + t * F + c), d);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float cdf = norm_cdf(g[e]);
+            du[e] = d[e] * g[e] * cdf;
+            dg[e] = d[e] * u[e] * (cdf + g[e] * 0.3989422804014327f * __expf(-0.5f * g[e] * g[e]));
+        }
+        *reinterpret_cast<u32x4*>(dgu + t * 2 * F + c) = pack8(du);
+        *reinterpret_cast<u32x4*>(dgu + t * 2 * F + F + c) = pack8(dg);
+    }
+}
+
+inline int flat_grid(int64_t items) {
+    int64_t g = (items + 255) / 256;
+    return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
+}
+
+}  // namespace
+
+#define ST(s) ((hipStream_t)(s))
+
+extern "C" int mi355_swa_attn_fwd(int B, int S, int Hq, int Hkv, int D, int W, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                                  int64_t ldv, void* o, int64_t ldo, float* lse, float scale, void* stream) {
+    if (check_swa("mi355_swa_attn_fwd", B, S, Hq, Hkv, D, W, ldq, ldk, ldv, ldo)) return 1;
+    if (B == 0 || S == 0) return 0;
+    MI355_REQUIRE(q && k && v && o && lse, "mi355_swa_attn_fwd: null pointer");
+    MI355_REQUIRE(aligned16({q, k, v, o}), "mi355_swa_attn_fwd: q, k, v, o must be 16-byte aligned");
+    const int w = W < S ? W : S;
+    dim3 grid((S + 127) / 128, Hq, B);
+#define LAUNCH(DD) swa_fwd_kernel<DD><<<grid, 256, 0, ST(stream)>>>(S, Hq, Hkv, w, (const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, lse, scale * LOG2E)
+    switch (D) {
+        case 32: LAUNCH(32); break;
+        case 64: LAUNCH(64); break;
+        default: LAUNCH(128); break;
+    }
+#undef LAUNCH
+    MI355_LAUNCH_CHECK("mi355_swa_attn_fwd");
+    return 0;
+}
+
+extern "C" int mi355_swa_attn_bwd(int B, int S, int Hq, int Hkv, int D, int W, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                                  int64_t ldv, const void* o, int64_t ldo, const void* d_o, int64_t lddo, const float* lse, float* delta, void* dq,
+                                  int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, float scale, void* stream) {
+    if (check_swa("mi355_swa_attn_bwd", B, S, Hq, Hkv, D, W, ldq, ldk, ldv, ldo)) return 1;
+    if (check_swa("mi355_swa_attn_bwd", B, S, Hq, Hkv, D, W, lddq, lddk, lddv, lddo)) return 1;
+    if (B == 0 || S == 0) return 0;
+    MI355_REQUIRE(q && k && v && o && d_o && lse && delta && dq && dk && dv, "mi355_swa_attn_bwd: null pointer");
+    MI355_REQUIRE(aligned16({q, k, v, d_o, dq, dk, dv}), "mi355_swa_attn_bwd: q, k, v, d_o, dq, dk, dv must be 16-byte aligned");
+    const int w = W < S ? W : S;
+    const int64_t tokens = (int64_t)B * S;
+    const int64_t dg = (tokens * Hq + 3) / 4;
+    swa_delta_kernel<<<(int)(dg > 8192 ? 8192 : dg), 256, 0, ST(stream)>>>(tokens, S, Hq, D, (const bf16_t*)o, ldo, (const bf16_t*)d_o, lddo, delta);
+    MI355_LAUNCH_CHECK("mi355_swa_attn_bwd(delta)");
+    dim3 gq((S + 127) / 128, Hq, B), gk((S + 127) / 128, Hkv, B);
+#define LAUNCH(DD)                                                                                                                                          \
+    swa_bwd_dq_kernel<DD><<<gq, 256, 0, ST(stream)>>>(S, Hq, Hkv, w, (const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (const bf16_t*)d_o, \
+                                                      lddo, lse, delta, (bf16_t*)dq, lddq, scale);                                                          \
+    swa_bwd_dkv_kernel<DD><<<gk, 256, 0, ST(stream)>>>(S, Hq, Hkv, w, (const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv,                   \
+                                                       (const bf16_t*)d_o, lddo, lse, delta, (bf16_t*)dk, lddk, (bf16_t*)dv, lddv, scale)
+    switch (D) {
+        case 32: LAUNCH(32); break;
+        case 64: LAUNCH(64); break;
+        default: LAUNCH(128); break;
+    }
+#undef LAUNCH
+    MI355_LAUNCH_CHECK("mi355_swa_attn_bwd");
+    return 0;
+}
+
+extern "C" int mi355_g3_rmsnorm_fwd(int64_t rows, int width, const void* x, const void* residual, const void* scale, void* y, float eps, void* stream) {
+    MI355_REQUIRE(rows >= 0 && width > 0 && (width & 7) == 0, "mi355_g3_rmsnorm_fwd: width must be a positive multiple of 8 (got %d)", width);
+    if (rows == 0) return 0;
+    MI355_REQUIRE(x && scale && y, "mi355_g3_rmsnorm_fwd: null pointer");
+    MI355_REQUIRE(aligned16({x, residual, scale, y}), "mi355_g3_rmsnorm_fwd: operands must be 16-byte aligned");
+    g3_rmsnorm_fwd_kernel<<<row_grid(rows), 256, 0, ST(stream)>>>(rows, width, (const bf16_t*)x, (const bf16_t*)residual, (const bf16_t*)scale, (bf16_t*)y, eps);
+    MI355_LAUNCH_CHECK("mi355_g3_rmsnorm_fwd");
+    return 0;
+}
+
+extern "C" int mi355_g3_rmsnorm_bwd(int64_t rows, int width, const void* x, const void* scale, const void* dy, const void* dres, void* dx,
+                                    float* dscale_partial, int parts, float eps, void* stream) {
+    MI355_REQUIRE(rows > 0 && width > 0 && (width & 7) == 0 && width <= 4096,
+                  "mi355_g3_rmsnorm_bwd: bad rows / width %d (multiple of 8, <= 4096: four per-wave LDS regions of width floats)", width);
+    MI355_REQUIRE(parts > 0 && parts <= 65535, "mi355_g3_rmsnorm_bwd: parts must be in 1..65535 (got %d)", parts);
+    MI355_REQUIRE(x && scale && dy && dx && dscale_partial, "mi355_g3_rmsnorm_bwd: null pointer");
+    MI355_REQUIRE(aligned16({x, scale, dy, dres, dx}), "mi355_g3_rmsnorm_bwd: operands must be 16-byte aligned");
+    g3_rmsnorm_bwd_kernel<<<parts, 256, 4 * width * sizeof(float), ST(stream)>>>(rows, width, (const bf16_t*)x, (const bf16_t*)scale, (const bf16_t*)dy,
+                                                                                 (const bf16_t*)dres, (bf16_t*)dx, dscale_partial, eps);
+    MI355_LAUNCH_CHECK("mi355_g3_rmsnorm_bwd");
+    return 0;
+}
+
+static int check_rope_ln(const char* who, int64_t tokens, int S, int Hq, int Hkv, int D, int64_t ldx, int64_t ldy, int64_t table_rows) {
+    MI355_REQUIRE(tokens >= 0 && S > 0 && Hq >= 0 && Hkv >= 0 && Hq + Hkv > 0, "%s: bad token / head counts", who);
+    MI355_REQUIRE(D == 32 || D == 64 || D == 128, "%s: head_dim %d not built (32, 64, 128)", who, D);
+    MI355_REQUIRE(ldx >= (int64_t)(Hq + Hkv) * D && ldy >= (int64_t)(Hq + Hkv) * D, "%s: leading dimension smaller than heads*head_dim", who);
+    MI355_REQUIRE(table_rows >= S, "%s: coefficient table has %lld rows, sequence length is %d", who, (long long)table_rows, S);
+    return 0;
+}
+
+extern "C" int mi355_g3_rope_ln_fwd(int64_t tokens, int S, int Hq, int Hkv, int D, const void* x, int64_t ldx, const float* cos_t, const float* sin_t,
+                                    int64_t table_rows, const void* q_scale, const void* q_shift, const void* k_scale, const void* k_shift, void* y,
+                                    int64_t ldy, float eps, void* stream) {
+    if (check_rope_ln("mi355_g3_rope_ln_fwd", tokens, S, Hq, Hkv, D, ldx, ldy, table_rows)) return 1;
+    if (tokens == 0) return 0;
+    MI355_REQUIRE(x && cos_t && sin_t && q_scale && q_shift && k_scale && k_shift && y, "mi355_g3_rope_ln_fwd: null pointer");
+    const int grid = row_grid(tokens * (Hq + Hkv) / (128 / D) + 1);
+#define LAUNCH(DD)                                                                                                                                      \
+    g3_rope_ln_kernel<DD, false><<<grid, 256, 0, ST(stream)>>>(tokens, S, Hq, Hkv, (const bf16_t*)x, ldx, cos_t, sin_t, (const bf16_t*)q_scale,           \
+                                                              (const bf16_t*)q_shift, (const bf16_t*)k_scale, (const bf16_t*)k_shift, nullptr, 0, (bf16_t*)y, \
+                                                              ldy, nullptr, eps)
+    switch (D) {
+        case 32: LAUNCH(32); break;
+        case 64: LAUNCH(64); break;
+        default: LAUNCH(128); break;
+    }
+#undef LAUNCH
+    MI355_LAUNCH_CHECK("mi355_g3_rope_ln_fwd");
+    return 0;
+}
+
+extern "C" int mi355_g3_rope_ln_bwd(int64_t tokens, int S, int Hq, int Hkv, int D, const void* x, int64_t ldx, const float* cos_t, const float* sin_t,
+                                    int64_t table_rows, const void* q_scale, const void* q_shift, const void* k_scale, const void* k_shift, const void* dy,
+                                    int64_t lddy, void* dx, int64_t lddx, float* partial, int parts, float eps, void* stream) {
+    if (check_rope_ln("mi355_g3_rope_ln_bwd", tokens, S, Hq, Hkv, D, ldx, lddy, table_rows)) return 1;
+    MI355_REQUIRE(lddx >= (int64_t)(Hq + Hkv) * D, "mi355_g3_rope_ln_bwd: leading dimension smaller than heads*head_dim");
+    MI355_REQUIRE(tokens > 0 && parts > 0 && parts <= 65535, "mi355_g3_rope_ln_bwd: tokens must be positive and parts in 1..65535 (got %d)", parts);
+    MI355_REQUIRE(x && cos_t && sin_t && q_scale && q_shift && k_scale && k_shift && dy && dx && partial, "mi355_g3_rope_ln_bwd: null pointer");
+#define LAUNCH(DD)                                                                                                                                      \
+    g3_rope_ln_kernel<DD, true><<<parts, 256, 0, ST(stream)>>>(tokens, S, Hq, Hkv, (const bf16_t*)x, ldx, cos_t, sin_t, (const bf16_t*)q_scale,           \
+                                                              (const bf16_t*)q_shift, (const bf16_t*)k_scale, (const bf16_t*)k_shift, (const bf16_t*)dy,  \
+                                                              lddy, (bf16_t*)dx, lddx, partial, eps)
+    switch (D) {
+        case 32: LAUNCH(32); break;
+        case 64: LAUNCH(64); break;
+        default: LAUNCH(128); break;
+    }
+#undef LAUNCH
+    MI355_LAUNCH_CHECK("mi355_g3_rope_ln_bwd");
+    return 0;
+}
+
+extern "C" int mi355_geglu_fwd(int64_t tokens, int F, const void* gu, void* a, void* stream) {
+    MI355_REQUIRE(tokens >= 0 && F > 0 && (F & 7) == 0, "mi355_geglu_fwd: F must be a positive multiple of 8 (got %d)", F);
+    if (tokens == 0) return 0;
+    MI355_REQUIRE(gu && a, "mi355_geglu_fwd: null pointer");
+    MI355_REQUIRE(aligned16({gu, a}), "mi355_geglu_fwd: operands must be 16-byte aligned");
+    g3_geglu_fwd_kernel<<<flat_grid(tokens * (F >> 3)), 256, 0, ST(stream)>>>(tokens, F, (const bf16_t*)gu, (bf16_t*)a);
+    MI355_LAUNCH_CHECK("mi355_geglu_fwd");
+    return 0;
+}
+
+extern "C" int mi355_geglu_bwd(int64_t tokens, int F, const void* gu, const void* da, void* dgu, void* stream) {
+    MI355_REQUIRE(tokens >= 0 && F > 0 && (F & 7) == 0, "mi355_geglu_bwd: F must be a positive multiple of 8 (got %d)", F);
+    if (tokens == 0) return 0;
+    MI355_REQUIRE(gu && da && dgu, "mi355_geglu_bwd: null pointer");
+    MI355_REQUIRE(aligned16({gu, da, dgu}), "mi355_geglu_bwd: operands must be 16-byte aligned");
+    g3_geglu_bwd_kernel<<<flat_grid(tokens * (F >> 3)), 256, 0, ST(stream)>>>(tokens, F, (const bf16_t*)gu, (const bf16_t*)da, (bf16_t*)dgu);
+    MI355_LAUNCH_CHECK("mi355_geglu_bwd");
+    return 0;
+}
