@@ -238,3 +238,14 @@ def dt_code(dtype):
     if dtype == torch.float32:
         return DT_F32
     raise TypeError(f"unsupported dtype {dtype}")
+
+
+def reduce_rows(part, out=None, accumulate=False):
+    """out[n] (+)= sum_p part[p, n], the fold of a backward kernel's per-workgroup partial rows; out fp32 / bf16 (new fp32 tensor if None)."""
+    parts, n = part.shape
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=part.device)
+        accumulate = False
+    require_gpu(part, out)
+    call("mi355_reduce_rows_f32", parts, n, ptr(part), ptr(out), dt_code(out.dtype), int(accumulate))
+    return out

@@ -10,20 +10,12 @@
 //   attn_decode_qkv the same attention started from the fused QKV stream's raw row: QK-RMSNorm + RoPE of the head's query and of its kv head's new key inside the launch,
 //                   key and value head written to the cache row at the device-side position (qknorm_rope_fwd + kv_append + attn_decode in one launch)
 //   argmax_rows     greedy sampling: first index of the row maximum (torch.argmax tie rule on ties is unspecified; first is used)
-#include "common.h"
+#include "rows_bf16.h"
 
 namespace {
 
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float MASK_T = -2.0e38f;  // finite "masked" score in the log2 domain (finfo(bf16).min / 2 semantics: exp -> 0, uniform if all masked)
-
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        f[2 * e] = __uint_as_float(v[e] << 16);
-        f[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u);
-    }
-}
 
 // ------------------------------------------------------------------------------------------- skinny GEMM (NT), M <= 8
 template <int MT>
@@ -55,14 +47,6 @@ __global__ __launch_bounds__(256) void gemv_kernel(int M, int64_t N, int K, cons
         if (lane == 0) y[m * ldy + n] = f2bf(res ? s + bf2f(res[m * ldr + n]) : s);
     }
 }
-
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-    u32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = pack_bf2(f[2 * e], f[2 * e + 1]);
-    return o;
-}
-__device__ __forceinline__ float rbf(float x) { return bf2f(f2bf(x)); }
 
 // The weight stream with its operand rows built in LDS first.  PRO 1: xs[m] = RMSNorm(x[m]) * nw, the arithmetic and summation order of rmsnorm_fwd_generic
 // (norm_rope.hip; == rmsnorm_fwd_kernel<2> at width 1024), so fused == the two launches bit for bit.  PRO 2: x holds gate-up rows [M, 2K] (up | gate, as the fused

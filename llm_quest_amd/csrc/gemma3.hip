@@ -18,80 +18,10 @@
 //   GeGLU (gemma3_transformer_block.py:101-106): a = lin1 * gelu_erf(lin_gate) on the fused [T, 2F] projection.
 #include <initializer_list>
 
-#include "common.h"
+#include "attn_tile32.h"
+#include "rows_bf16.h"
 
 namespace {
-
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
-#define NEG_INF (-__builtin_huge_valf())
-
-template <int D>
-struct SW {
-    static constexpr int PITCH = D * 2 + 16;  // bytes per LDS row
-    static constexpr int KS = D / 16;         // k-steps over d
-    static constexpr int DT = D / 32;         // 32-row tiles of a transposed [d x 32] accumulator
-    static constexpr int IMG = 32 * PITCH;    // one 32-row image
-};
-
-// cooperative load of 32 rows x D bf16 into a padded LDS image; rows >= rows_valid are zero
-template <int D>
-__device__ __forceinline__ void load_tile(char* img, const bf16_t* base, int64_t ld, int rows_valid, int tid) {
-    constexpr int CH = D / 8;
-    for (int c = tid; c < 32 * CH; c += 256) {
-        const int row = c / CH, ch = c % CH;
-        u32x4 v = {0, 0, 0, 0};
-        if (row < rows_valid) v = *reinterpret_cast<const u32x4*>(base + (int64_t)row * ld + ch * 8);
-        *reinterpret_cast<u32x4*>(img + row * SW<D>::PITCH + ch * 16) = v;
-    }
-}
-// A operand (32 rows x 16 k) from a row image: row = lane & 31, k = 16 ks + 8 (lane >> 5) ..
-template <int D>
-__device__ __forceinline__ bf16x8 frag_rows(const char* img, int ks, int lane) {
-    return *reinterpret_cast<const bf16x8*>(img + (lane & 31) * SW<D>::PITCH + (2 * ks + (lane >> 5)) * 16);
-}
-// A operand of the TRANSPOSE of a row image: rows of A = image columns c0 .. c0+31, k = image rows in the order in which an accumulator tile
-// packs into a B operand: element j <-> image row k0 + 8 (j >> 2) + 4 (lane >> 5) + (j & 3)
-template <int D>
-__device__ __forceinline__ bf16x8 frag_cols(const char* img, int c0, int k0, int lane) {
-    const int g = lane >> 4, q4 = (lane >> 2) & 3, p = lane & 3;
-    const int row = k0 + 4 * (g >> 1) + q4;
-    const int col = c0 + 16 * (g & 1) + 4 * p;
-    const char* a = img + row * SW<D>::PITCH + col * 2;
-    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(a));
-    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(a + 8 * SW<D>::PITCH));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-__device__ __forceinline__ bf16x8 pack_frag(const f32x16& x, int s) {
-    u32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = pack_bf2(x[8 * s + 2 * e], x[8 * s + 2 * e + 1]);
-    return __builtin_bit_cast(bf16x8, o);
-}
-// B operand fragments of a row held on the lane (row = lane & 31 of the wave's 32 rows)
-template <int D>
-__device__ __forceinline__ void load_row_frags(const bf16_t* rowptr, bool valid, int lane, bf16x8 (&f)[SW<D>::KS]) {
-#pragma unroll
-    for (int ks = 0; ks < SW<D>::KS; ++ks) {
-        u32x4 v = {0, 0, 0, 0};
-        if (valid) v = *reinterpret_cast<const u32x4*>(rowptr + 16 * ks + 8 * (lane >> 5));
-        f[ks] = __builtin_bit_cast(bf16x8, v);
-    }
-}
-// accumulator tile [32 d x 32 rows-on-lane] -> token-major bf16 rows (4 consecutive d per 8-byte store)
-template <int NDT>
-__device__ __forceinline__ void store_t_tiles(const f32x16 (&acc)[NDT], float mul, bf16_t* rowptr, bool valid, int lane) {
-    if (!valid) return;
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-        for (int i4 = 0; i4 < 4; ++i4) {
-            u32x2 w;
-            w[0] = pack_bf2(acc[dt][4 * i4] * mul, acc[dt][4 * i4 + 1] * mul);
-            w[1] = pack_bf2(acc[dt][4 * i4 + 2] * mul, acc[dt][4 * i4 + 3] * mul);
-            *reinterpret_cast<u32x2*>(rowptr + 32 * dt + 8 * i4 + 4 * (lane >> 5)) = w;
-        }
-}
 
 // ------------------------------------------------------------------------------------------------ sliding-window attention, forward
 // W is already clamped to [1, S] and S <= 2^30 - 64 (check_swa): every sum of an index and W below stays inside int.
@@ -99,7 +29,7 @@ template <int D>
 __global__ __launch_bounds__(256) void swa_fwd_kernel(int S, int Hq, int Hkv, int W, const bf16_t* __restrict__ q, int64_t ldq,
                                                       const bf16_t* __restrict__ k, int64_t ldk, const bf16_t* __restrict__ v, int64_t ldv,
                                                       bf16_t* __restrict__ o, int64_t ldo, float* __restrict__ lse, float scale_log2) {
-    using C = SW<D>;
+    using C = Tile32<D>;
     __shared__ __attribute__((aligned(16))) char smem[2 * C::IMG];
     char* kimg = smem;
     char* vimg = smem + C::IMG;
@@ -123,8 +53,8 @@ __global__ __launch_bounds__(256) void swa_fwd_kernel(int S, int Hq, int Hkv, in
     for (int kt = kfirst / 32; kt <= qlast / 32; ++kt) {
         const int key0 = kt * 32;
         __syncthreads();
-        load_tile<D>(kimg, k + (tok0 + key0) * ldk + (int64_t)hkv * D, ldk, S - key0, threadIdx.x);
-        load_tile<D>(vimg, v + (tok0 + key0) * ldv + (int64_t)hkv * D, ldv, S - key0, threadIdx.x);
+        load_tile<D, 256>(kimg, k + (tok0 + key0) * ldk + (int64_t)hkv * D, ldk, S - key0, threadIdx.x);
+        load_tile<D, 256>(vimg, v + (tok0 + key0) * ldv + (int64_t)hkv * D, ldv, S - key0, threadIdx.x);
         __syncthreads();
         // tile above this wave's diagonal, or wholly before the window of its first query (later queries' windows start later still)
         if (q0 >= S || key0 > q0 + 31 || key0 + 31 + W <= q0) continue;
@@ -169,28 +99,13 @@ __global__ __launch_bounds__(256) void swa_fwd_kernel(int S, int Hq, int Hkv, in
     if (lane < 32 && qvalid) lse[((int64_t)b * Hq + h) * S + query] = (m + log2f(l)) * LN2;
 }
 
-// delta[b, h, s] = sum_d dO * O
-__global__ __launch_bounds__(256) void swa_delta_kernel(int64_t tokens, int S, int Hq, int D, const bf16_t* __restrict__ o, int64_t ldo,
-                                                        const bf16_t* __restrict__ d_o, int64_t lddo, float* __restrict__ delta) {
-    const int lane = threadIdx.x & 63;
-    const int64_t total = tokens * Hq;
-    for (int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); item < total; item += (int64_t)gridDim.x * 4) {
-        const int64_t t = item / Hq;
-        const int h = (int)(item % Hq);
-        float acc = 0.f;
-        for (int i = lane; i < D; i += 64) acc += bf2f(o[t * ldo + (int64_t)h * D + i]) * bf2f(d_o[t * lddo + (int64_t)h * D + i]);
-        acc = wave_sum(acc);
-        if (lane == 0) delta[((t / S) * Hq + h) * S + (t % S)] = acc;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ dQ pass (query-major, the forward's band)
 template <int D>
 __global__ __launch_bounds__(256) void swa_bwd_dq_kernel(int S, int Hq, int Hkv, int W, const bf16_t* __restrict__ q, int64_t ldq,
                                                          const bf16_t* __restrict__ k, int64_t ldk, const bf16_t* __restrict__ v, int64_t ldv,
                                                          const bf16_t* __restrict__ d_o, int64_t lddo, const float* __restrict__ lse,
                                                          const float* __restrict__ delta, bf16_t* __restrict__ dq, int64_t lddq, float scale) {
-    using C = SW<D>;
+    using C = Tile32<D>;
     __shared__ __attribute__((aligned(16))) char smem[2 * C::IMG];
     char* kimg = smem;
     char* vimg = smem + C::IMG;
@@ -217,8 +132,8 @@ __global__ __launch_bounds__(256) void swa_bwd_dq_kernel(int S, int Hq, int Hkv,
     for (int kt = kfirst / 32; kt <= qlast / 32; ++kt) {
         const int key0 = kt * 32;
         __syncthreads();
-        load_tile<D>(kimg, k + (tok0 + key0) * ldk + (int64_t)hkv * D, ldk, S - key0, threadIdx.x);
-        load_tile<D>(vimg, v + (tok0 + key0) * ldv + (int64_t)hkv * D, ldv, S - key0, threadIdx.x);
+        load_tile<D, 256>(kimg, k + (tok0 + key0) * ldk + (int64_t)hkv * D, ldk, S - key0, threadIdx.x);
+        load_tile<D, 256>(vimg, v + (tok0 + key0) * ldv + (int64_t)hkv * D, ldv, S - key0, threadIdx.x);
         __syncthreads();
         if (q0 >= S || key0 > q0 + 31 || key0 + 31 + W <= q0) continue;
         f32x16 s, dp;
@@ -254,7 +169,7 @@ __global__ __launch_bounds__(256) void swa_bwd_dkv_kernel(int S, int Hq, int Hkv
                                                           const bf16_t* __restrict__ d_o, int64_t lddo, const float* __restrict__ lse,
                                                           const float* __restrict__ delta, bf16_t* __restrict__ dk, int64_t lddk,
                                                           bf16_t* __restrict__ dv, int64_t lddv, float scale) {
-    using C = SW<D>;
+    using C = Tile32<D>;
     constexpr int NDT = C::DT;
     __shared__ __attribute__((aligned(16))) char smem[2 * C::IMG];
     __shared__ float stat[2][32];
@@ -282,8 +197,8 @@ __global__ __launch_bounds__(256) void swa_bwd_dkv_kernel(int S, int Hq, int Hkv
         for (int qt = kb / 32; qt <= qend / 32; ++qt) {
             const int qs = qt * 32;
             __syncthreads();
-            load_tile<D>(qimg, q + (tok0 + qs) * ldq + (int64_t)hq * D, ldq, S - qs, threadIdx.x);
-            load_tile<D>(gimg, d_o + (tok0 + qs) * lddo + (int64_t)hq * D, lddo, S - qs, threadIdx.x);
+            load_tile<D, 256>(qimg, q + (tok0 + qs) * ldq + (int64_t)hq * D, ldq, S - qs, threadIdx.x);
+            load_tile<D, 256>(gimg, d_o + (tok0 + qs) * lddo + (int64_t)hq * D, lddo, S - qs, threadIdx.x);
             if (threadIdx.x < 32) {
                 const bool okq = qs + threadIdx.x < S;
                 stat[0][threadIdx.x] = okq ? lse[((int64_t)b * Hq + hq) * S + qs + threadIdx.x] * LOG2E : 0.f;
@@ -344,21 +259,6 @@ int check_swa(const char* who, int B, int S, int Hq, int Hkv, int D, int W, int6
 }
 
 // ------------------------------------------------------------------------------------------------ row helpers
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        f[2 * e] = __uint_as_float(v[e] << 16);
-        f[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-    u32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = pack_bf2(f[2 * e], f[2 * e + 1]);
-    return o;
-}
-__device__ __forceinline__ float rbf(float x) { return bf2f(f2bf(x)); }
-
 inline int row_grid(int64_t rows) {
     int64_t g = (rows + 3) / 4;
     return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
@@ -607,7 +507,7 @@ extern "C" int mi355_swa_attn_bwd(int B, int S, int Hq, int Hkv, int D, int W, c
     const int w = W < S ? W : S;
     const int64_t tokens = (int64_t)B * S;
     const int64_t dg = (tokens * Hq + 3) / 4;
-    swa_delta_kernel<<<(int)(dg > 8192 ? 8192 : dg), 256, 0, ST(stream)>>>(tokens, S, Hq, D, (const bf16_t*)o, ldo, (const bf16_t*)d_o, lddo, delta);
+    attn_delta_kernel<<<(int)(dg > 8192 ? 8192 : dg), 256, 0, ST(stream)>>>(tokens, S, Hq, D, (const bf16_t*)o, ldo, (const bf16_t*)d_o, lddo, delta);
     MI355_LAUNCH_CHECK("mi355_swa_attn_bwd(delta)");
     dim3 gq((S + 127) / 128, Hq, B), gk((S + 127) / 128, Hkv, B);
 #define LAUNCH(DD)                                                                                                                                          \

@@ -8,29 +8,15 @@
 // the full-row reductions (sums of squares, the (n + 2) * n dot products) are wave shuffles + one LDS exchange between the waves, summed in a
 // fixed order.  The column-wise parameter gradients of the backward therefore never cross threads: a thread accumulates its own columns over the
 // workgroup's tokens and writes them into the workgroup's row of partials; mi355_reduce_rows_f32 folds the rows.  No atomics anywhere.
-#include "common.h"
+#include "rows_bf16.h"
 
 namespace {
 
 constexpr int HC_MAX_THREADS = 512;
 constexpr int HC_SMALL_THREADS = 256;  // d <= 2048
 
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        f[2 * e] = __uint_as_float(v[e] << 16);
-        f[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-    u32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = pack_bf2(f[2 * e], f[2 * e + 1]);
-    return o;
-}
 // element e (a compile-time constant after unrolling) of 8 packed bf16: the streams stay packed in registers and are widened where they are used
 __device__ __forceinline__ float el(const u32x4 v, int e) { return __uint_as_float((e & 1) ? (v[e >> 1] & 0xffff0000u) : (v[e >> 1] << 16)); }
-__device__ __forceinline__ float rbf(float x) { return bf2f(f2bf(x)); }  // round through bf16
 __device__ __forceinline__ void load8f(const float* p, float (&f)[8]) {
     const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
 #pragma unroll

@@ -13,29 +13,15 @@
 //                        independent recurrence, so rows are spread over lanes and the time loop runs inside the kernel
 //   gated_rmsnorm        RMSNorm(fp32) * silu(gate) -> bf16
 //   rowmask              x * padding_mask
-#include "common.h"
+#include "rows_bf16.h"
 
 namespace {
 
-__device__ __forceinline__ float rbf(float x) { return bf2f(f2bf(x)); }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ float silu_f(float x) { return x / (1.f + expf(-x)); }
 __device__ __forceinline__ float dsilu_f(float x) {
     const float s = sigmoid_f(x);
     return s * (1.f + x * (1.f - s));
-}
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        f[2 * e] = __uint_as_float(v[e] << 16);
-        f[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-    u32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = pack_bf2(f[2 * e], f[2 * e + 1]);
-    return o;
 }
 // Cross-lane sums on the VALU (DPP / permlane swaps), not through the LDS crossbar: ds_bpermute (what __shfl_xor compiles to)
 // costs an LDS round trip per step of every reduction, and the recurrence kernels below are one dependent chain per time step.

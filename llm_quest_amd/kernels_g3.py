@@ -127,9 +127,7 @@ def rmsnorm_bwd(x, scale, dy, dres=None, eps=RMS_EPS, parts=None):
     dx = torch.empty_like(x)
     part = torch.empty((parts, width), dtype=F32, device=x.device)
     L.call("mi355_g3_rmsnorm_bwd", rows, width, L.ptr(x), L.ptr(scale), L.ptr(dy), L.ptr(dres), L.ptr(dx), L.ptr(part), parts, eps)
-    dscale = torch.empty(width, dtype=F32, device=x.device)
-    L.call("mi355_reduce_rows_f32", parts, width, L.ptr(part), L.ptr(dscale), L.DT_F32, 0)
-    return dx, dscale
+    return dx, L.reduce_rows(part)
 
 
 def _check_rope_ln(name, x, S, Hq, Hkv, D, cos, sin, params):
@@ -179,8 +177,7 @@ def rope_ln_bwd(x, dy, S, Hq, Hkv, D, cos, sin, q_scale, q_shift, k_scale, k_shi
     part = torch.empty((parts, 4 * D), dtype=F32, device=x.device)
     L.call("mi355_g3_rope_ln_bwd", T, S, Hq, Hkv, D, L.ptr(x), max(x.stride(0), width), L.ptr(cos), L.ptr(sin), cos.shape[0], *[L.ptr(p) for p in params],
            L.ptr(dy), max(dy.stride(0), width), L.ptr(dx), max(dx.stride(0), width), L.ptr(part), parts, eps)
-    row = torch.empty(4 * D, dtype=F32, device=x.device)
-    L.call("mi355_reduce_rows_f32", parts, 4 * D, L.ptr(part), L.ptr(row), L.DT_F32, 0)
+    row = L.reduce_rows(part)
     return dx, row[:D], row[D : 2 * D], row[2 * D : 3 * D], row[3 * D :]
 
 

@@ -144,8 +144,7 @@ def width_bwd(dR, dP, dh_post, X, H, TH, rstd, c, parts=None):
     partial = torch.empty((parts, pw), dtype=F32, device=dev)
     L.call("mi355_hc_width_bwd", T, n, d, L.ptr(dR), L.ptr(dP), L.ptr(dh_post), L.ptr(X), L.ptr(H), L.ptr(TH), L.ptr(rstd), L.ptr(c.w_norm),
            L.ptr(c.W_res), L.ptr(c.w_pre), L.ptr(c.w_post), L.ptr(c.f_res), L.ptr(c.f_pre), L.ptr(c.f_post), L.ptr(dX), L.ptr(partial), parts)
-    row = torch.empty(pw, dtype=F32, device=dev)
-    L.call("mi355_reduce_rows_f32", parts, pw, L.ptr(partial), L.ptr(row), L.DT_F32, 0)
+    row = L.reduce_rows(partial)
     o = (n + 3) * d
     g = WidthGrads(
         W_res=row[: n * d].view(n, d), w_pre=row[n * d : (n + 1) * d], w_post=row[(n + 1) * d : (n + 2) * d], w_norm=row[(n + 2) * d : o],

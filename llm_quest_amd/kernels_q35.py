@@ -19,17 +19,6 @@ def _cols(t, name, dtype=BF16):
         raise ValueError(f"{name}: expected a 2-D {dtype} tensor with unit inner stride, got {t.dtype} {tuple(t.shape)} {t.stride()}")
 
 
-def _reduce_parts(part, out=None, accumulate=False):
-    """out[n] (+)= sum_p part[p, n]; out fp32 / bf16 (new fp32 tensor if None)."""
-    parts, n = part.shape
-    if out is None:
-        out = torch.empty(n, dtype=F32, device=part.device)
-        accumulate = False
-    L.require_gpu(part, out)
-    L.call("mi355_reduce_rows_f32", parts, n, L.ptr(part), L.ptr(out), L.dt_code(out.dtype), int(accumulate))
-    return out
-
-
 def zc_weight(scale):
     """bf16(1 + scale) of ZeroCenteredRMSNorm."""
     L.require_gpu(scale)
@@ -105,7 +94,7 @@ def headnorm_rope_bwd(src, H, D, head_stride, w_eff, cos_t, sin_t, pos, rstd, do
     part = torch.empty((parts, D), dtype=F32, device=src.device)
     L.call("mi355_headnorm_rope_bwd", tokens, H, D, R, L.ptr(src), src.stride(0), head_stride, L.ptr(w_eff), L.ptr(cos_t), L.ptr(sin_t), L.ptr(pos), L.ptr(rstd),
            L.ptr(dout), L.ptr(dsrc), dsrc.stride(0), dhead_stride, L.ptr(part), parts)
-    return _reduce_parts(part)
+    return L.reduce_rows(part)
 
 
 def sigmoid_gate_fwd(ctx, gate, H, D, gate_head_stride):
@@ -183,7 +172,7 @@ def gdn_gates_bwd(b_lin, a_lin, log_A, dt_bias, dbeta, dalpha, db_lin, da_lin):
     part = torch.empty((parts, 2 * Hv), dtype=F32, device=b_lin.device)
     L.call("mi355_gdn_gates_bwd", tokens, Hv, L.ptr(b_lin), L.ptr(a_lin), b_lin.stride(0), L.ptr(log_A), L.ptr(dt_bias), L.ptr(dbeta), L.ptr(dalpha),
            L.ptr(db_lin), L.ptr(da_lin), db_lin.stride(0), L.ptr(part), parts)
-    both = _reduce_parts(part)
+    both = L.reduce_rows(part)
     return both[:Hv], both[Hv:]
 
 
@@ -226,7 +215,7 @@ def causal_conv_silu_bwd(x, w, dy, dx, B, S):
     chunks = B * ((S + CONV_TOKEN_CHUNK - 1) // CONV_TOKEN_CHUNK)
     part = torch.empty((chunks, C * ks), dtype=F32, device=x.device)
     L.call("mi355_causal_conv_silu_bwd", B, S, C, ks, L.ptr(x), x.stride(0), L.ptr(w), L.ptr(dy), L.ptr(ws), L.ptr(dx), dx.stride(0), L.ptr(part), CONV_TOKEN_CHUNK)
-    return _reduce_parts(part)
+    return L.reduce_rows(part)
 
 
 def l2norm_fwd(x, H, D):
@@ -333,4 +322,4 @@ def gated_rmsnorm_bwd(o, w_f32, gate, rstd, dout, dgate, H, D):
     parts = max(1, min(NORM_PARTS, (o.shape[0] * H + 3) // 4))
     part = torch.empty((parts, D), dtype=F32, device=o.device)
     L.call("mi355_gated_rmsnorm_bwd", o.shape[0], H, D, L.ptr(o), L.ptr(w_f32), L.ptr(gate), gate.stride(0), L.ptr(rstd), L.ptr(dout), L.ptr(d_o), L.ptr(dgate), dgate.stride(0), L.ptr(part), parts)
-    return d_o, _reduce_parts(part)
+    return d_o, L.reduce_rows(part)

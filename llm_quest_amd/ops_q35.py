@@ -53,7 +53,7 @@ def _f32_param_grad(p, g_f32):
     if p.grad is None:
         p.grad = g.clone()
     else:
-        Q._reduce_parts(g.reshape(1, -1).contiguous(), out=p.grad.view(-1), accumulate=True)
+        L.reduce_rows(g.reshape(1, -1).contiguous(), out=p.grad.view(-1), accumulate=True)
 
 
 class Runtime:
