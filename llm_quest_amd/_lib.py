@@ -123,6 +123,11 @@ SIGNATURES = {
     "mi355_g3_rope_ln_bwd": [_L, _I, _I, _I, _I, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, _L, _P, _I, _F, _P],
     "mi355_geglu_fwd": [_L, _I, _P, _P, _P],
     "mi355_geglu_bwd": [_L, _I, _P, _P, _P, _P],
+    # DeepSeek-V3: Multi-head Latent Attention and the decoupled RoPE (csrc/deepseek.hip)
+    "mi355_mla_attn_fwd": [_I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _F, _P],
+    "mi355_mla_attn_bwd": [_I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _L, _P, _L, _P, _L, _P, _P, _L, _F, _P],
+    "mi355_mla_rope_fwd": [_L, _I, _I, _I, _P, _L, _P, _L, _P, _P, _L, _P, _L, _P, _L, _P],
+    "mi355_mla_rope_bwd": [_L, _I, _I, _I, _P, _L, _P, _P, _P, _L, _P, _L, _P, _L, _P],
 }
 # size / constant queries: no stream argument, the return value is the answer (name -> (argtypes, restype))
 QUERIES = {
