@@ -413,7 +413,9 @@ _ATTN_ABLATE = int(os.environ.get("MI355_ATTN_ABLATE", "0")) << 8  # profiling s
 _ATTN_DS_SPILL = os.environ.get("MI355_ATTN_DS_SPILL", "1") != "0"  # 0: the dQ pass recomputes S and dP (no scratch)
 # The dS scratch grows with S^2 (2 bytes per (query, key) of the padded square per head): 1.2 GB at the headline shape, 17 GB at S = 8192, B = 8.
 # Above this cap -- or a quarter of the device's free memory, or when the allocation fails -- the backward takes the recompute form (three
-# products in the dQ pass, O(S) memory, bit-identical gradients): long-context training keeps working, only slower per layer.
+# products in the dQ pass, O(S) memory): long-context training keeps working, only slower per layer.  The two forms agree to the bf16 level of
+# a gradient, not bit for bit: the spill form's dK/dV pass folds the scale into its bf16 K rows, one more rounding of an operand
+# (test_attention_backward_scratch_form_equals_recompute_form); each is held to fp64 block by block in tests/test_attention_sweep_gpu.py.
 _ATTN_DS_SPILL_MAX = int(float(os.environ.get("MI355_ATTN_DS_SPILL_MAX_MB", "4096")) * (1 << 20))
 _ATTN_WS = {}  # (device, stream handle) -> uint8 buffer; at most _ATTN_WS_SLOTS entries (least recently used dropped: dead streams do not pin memory)
 _ATTN_WS_SLOTS = 4
@@ -466,7 +468,13 @@ def attn_fwd(q, k, v, B, S, Hq, Hkv, D, key_mask=None, causal=True, scale=None):
 
 
 def attn_bwd(q, k, v, o, do, lse, B, S, Hq, Hkv, D, dq, dk, dv, key_mask=None, causal=True, scale=None):
-    """dq/dk/dv are caller-provided (possibly row-strided) destinations."""
+    """dq/dk/dv are caller-provided (possibly row-strided) destinations; every row of them is written.
+
+    The backward treats a fully-masked row as contributing nothing.  This equals the reference wherever dO is zero on such rows.  Otherwise dV lacks
+    (1/S)·Σ dO of those rows.  (A fully-masked row is a query whose visible keys are all padding -- the rows in front of the first real key of a
+    left-padded sample under the causal mask.  The forward gives it the reference's uniform attention over all S keys; the reference's autograd
+    sends dq = 0 and no dk through it, but (1/S) dO[i] into dV of every key of the sample.  A loss that ignores padded positions leaves dO zero there
+    in every layer; tests/test_attention_sweep_gpu.py::test_attention_backward_left_padding pins both sides.)"""
     L.require_gpu(q, k, v, o, do, lse, dq, dk, dv)
     for t, n, w in ((q, "q", Hq), (k, "k", Hkv), (v, "v", Hkv), (o, "o", Hq), (do, "do", Hq), (dq, "dq", Hq), (dk, "dk", Hkv), (dv, "dv", Hkv)):
         _check_attn_operand(t, n, B * S, w * D)

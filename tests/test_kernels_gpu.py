@@ -644,6 +644,45 @@ def test_out_projection_dgrad_leaves_the_attention_backwards_row_constants(K, B,
     assert K.dgrad_attn_delta(dy[: 2 * S], w, ctx[: 2 * S], lse[:2].contiguous(), 2, S, Hq, D) is None
 
 
+@pytest.mark.parametrize("Hq", [3, 6])
+def test_out_projection_dgrad_row_constants_under_the_weight_stationary_walk(K, Hq, monkeypatch):
+    """The case of the test above that the library's own choice never reaches in it: mi355_gemm_bf16_attn_delta in the persistent kernel's
+    weight-stationary walk (MI355_GEMM_WALK=1; by shape from K >= 2048).  Hq * 128 / 256 is no multiple of 4 (1.5 and 3 column panels: the walk's
+    column group ends in empty tiles, and at Hq = 3 the last real tile holds one head), M = 9 * 500 is ragged: d(ctx), delta and both row-constant
+    arrays of the backward's scratch are the bits of the MI355_GEMM_WALK=0 run."""
+    from llm_quest_amd import _lib as L
+
+    B, S, D, d_model = 9, 500, 128, 2048
+    g = torch.Generator().manual_seed(43 + Hq)
+    ctx = dev(torch.randn(B * S, Hq * D, generator=g).to(BF16))
+    lse = dev(torch.randn(B, Hq, S, generator=g) * 3)
+    dy = dev((0.05 * torch.randn(B * S, d_model, generator=g)).to(BF16))
+    w = dev((0.05 * torch.randn(d_model, Hq * D, generator=g)).to(BF16))
+    lib = L.load()
+    need = lib.mi355_attn_bwd_workspace_bytes(B, S, Hq, D)
+    n = B * Hq * S
+    offs = [lib.mi355_attn_bwd_workspace_rowconst_offset(B, S, Hq, D, i) for i in (0, 1)]
+    monkeypatch.setenv("MI355_GEMM_PERSIST_MIN_TILES", "1")
+    runs = []
+    for walk in ("0", "1"):
+        monkeypatch.setenv("MI355_GEMM_WALK", walk)
+        ws = K._attn_scratch(dy.device, need)
+        ws[offs[0] : offs[0] + 4 * n].view(torch.float32).fill_(float("nan"))
+        ws[offs[1] : offs[1] + 4 * n].view(torch.float32).fill_(float("nan"))
+        fused = K.dgrad_attn_delta(dy, w, ctx, lse, B, S, Hq, D)
+        assert fused is not None
+        ws2 = K._attn_scratch(dy.device, need)
+        assert ws2.data_ptr() == ws.data_ptr()
+        runs.append((fused[0], fused[1], ws2[offs[0] : offs[0] + 4 * n].view(torch.float32).clone(), ws2[offs[1] : offs[1] + 4 * n].view(torch.float32).clone()))
+    for name, a, b in zip(("d(ctx)", "delta", "-lse * log2(e)", "-delta"), *runs):
+        assert torch.isfinite(b.float()).all() and torch.equal(a, b), name
+    dctx, delta, nl2, ndl = runs[1]
+    assert rel_l2(dctx, dy.float() @ w.float()) < 3e-3  # one bf16 rounding of the output
+    want = (dctx.float() * ctx.float()).view(B, S, Hq, D).sum(-1).permute(0, 2, 1).contiguous()
+    assert rel_l2(delta, want) < 1e-5
+    assert torch.equal(ndl.view(B, Hq, S), -delta) and torch.equal(nl2.view(B, Hq, S), -lse * torch.tensor(1.4426950408889634, dtype=torch.float32, device=lse.device))
+
+
 def test_attention_strided_views(K):
     """k/v read in place from the fused QKV projection buffer (row pitch = (Hq+2Hkv)*D)."""
     B, S, Hq, Hkv, D = 1, 100, 4, 2, 128
