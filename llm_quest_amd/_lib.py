@@ -128,6 +128,13 @@ SIGNATURES = {
     "mi355_mla_attn_bwd": [_I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _L, _P, _L, _P, _L, _P, _P, _L, _F, _P],
     "mi355_mla_rope_fwd": [_L, _I, _I, _I, _P, _L, _P, _L, _P, _P, _L, _P, _L, _P, _L, _P],
     "mi355_mla_rope_bwd": [_L, _I, _I, _I, _P, _L, _P, _P, _P, _L, _P, _L, _P, _L, _P],
+    # Qwen3 mixture-of-experts: router, token-to-expert plan, row dispatch and weighted combine (csrc/moe.hip)
+    "mi355_moe_route_fwd": [_L, _I, _I, _P, _L, _I, _P, _L, _P, _P, _P, _P],
+    "mi355_moe_route_bwd": [_L, _I, _I, _P, _P, _P, _P, _P, _L, _P, _P, _F, _P, _L, _P],
+    "mi355_moe_plan": [_L, _I, _I, _P, _P, _P, _P, _P, _L, _P, _F, _P, _P, _L, _P],
+    "mi355_moe_gather_rows": [_L, _L, _I, _P, _P, _L, _P, _L, _P],
+    "mi355_moe_combine_fwd": [_L, _L, _I, _I, _P, _P, _P, _L, _P, _L, _P, _L, _P],
+    "mi355_moe_combine_bwd": [_L, _L, _I, _I, _P, _P, _P, _P, _L, _P, _L, _P, _L, _P, _P],
 }
 # size / constant queries: no stream argument, the return value is the answer (name -> (argtypes, restype))
 QUERIES = {
@@ -138,6 +145,8 @@ QUERIES = {
     "mi355_attn_bwd_qnorm_partials": ([_I, _I, _I], _L),
     "mi355_embedding_bwd_sorted_workspace_bytes": ([_L, _I], _L),
     "mi355_hc_width_bwd_partial_width": ([_I, _I], _L),
+    "mi355_moe_row_align": ([], _I),
+    "mi355_moe_plan_workspace_bytes": ([_L, _I, _I], _L),
 }
 
 _lib = None

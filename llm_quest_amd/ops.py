@@ -159,17 +159,38 @@ def _put_rows(g2d, B, S, rows):
     return full
 
 
+def attention_half_forward(blk, arena, x, rt):
+    """x + att(norm1(x)) of a pre-norm block, the residual add on the out-projection's epilogue: (x2 [M, d], what the backward needs).  Shared by the
+    dense block and the mixture-of-experts block (ops_moe)."""
+    h1, rstd1 = K.rmsnorm_fwd(x, blk.norm1.weight)
+    ctx, att_saved = attention_forward(blk.att, arena, h1, rt)
+    x2 = K.gemm(L.GEMM_NT, ctx, blk.att.out_proj.weight, residual=x)
+    return x2, (h1, rstd1, ctx, att_saved)
+
+
+def attention_half_backward(blk, arena, x, saved, dx2, rt, wg):
+    """Its backward: d(x) from d(x2), the residual's share included; the weight gradients are recorded in ``wg``."""
+    att = blk.att
+    h1, rstd1, ctx, att_saved = saved
+    # the softmax backward's row sums (delta) are the epilogue of the out-projection's dgrad when the shape allows
+    fused = K.dgrad_attn_delta(dx2, att.out_proj.weight, ctx, att_saved[4], rt.B, rt.S, att.num_heads, att.head_dim)
+    dctx, delta = fused if fused is not None else (K.dgrad(dx2, att.out_proj.weight), None)
+    _wgrad(arena, att.out_proj.weight, None, dx2, ctx, wg)
+    dh1 = attention_backward(att, arena, h1, ctx, att_saved, dctx, rt, wg, delta)
+    gview, gacc = _vecgrad(arena, blk.norm1.weight)
+    dx, _ = K.rmsnorm_bwd(x, blk.norm1.weight, rstd1, dh1, dres=dx2, dw_out=gview, dw_accumulate=gacc)
+    return dx
+
+
 def block_forward(blk, x, rt, keep, rows=None):
     """``rows`` = (lo, hi): only these rows of every sample are needed downstream (the decoder's LAST block in the early-fusion step: the loss reads the
     512 rows that predict text tokens, so the 197 others feed nothing once their keys and values have been used).  The attention half runs on the
     whole sequence, the FFN half -- 60 % of the block's arithmetic -- on the kept rows only, and the block returns [B*(hi-lo), d].  Same results on
     the kept rows, bit for bit: every kernel of the FFN half works row by row."""
     arena = arena_for(blk)
-    att, ffn = blk.att, blk.ffn
+    ffn = blk.ffn
     F_ = ffn.lin1.weight.shape[0]
-    h1, rstd1 = K.rmsnorm_fwd(x, blk.norm1.weight)
-    ctx, att_saved = attention_forward(att, arena, h1, rt)
-    x2 = K.gemm(L.GEMM_NT, ctx, att.out_proj.weight, residual=x)
+    x2, (h1, rstd1, ctx, att_saved) = attention_half_forward(blk, arena, x, rt)
     if rows is not None:
         x2 = _take_rows(x2, rt.B, rt.S, rows)
     h2, rstd2 = K.rmsnorm_fwd(x2, blk.norm2.weight)
@@ -185,7 +206,7 @@ def block_forward(blk, x, rt, keep, rows=None):
 
 def block_backward(blk, saved, dx3, rt, rows=None):
     arena = arena_for(blk)
-    att, ffn = blk.att, blk.ffn
+    ffn = blk.ffn
     F_ = ffn.lin1.weight.shape[0]
     x, h1, rstd1, ctx, att_saved, x2, h2, rstd2, gu, a = saved
     wg = []  # the four weight-gradient GEMMs run as one grouped launch at the end (their operands stay alive until then)
@@ -202,14 +223,7 @@ def block_backward(blk, saved, dx3, rt, rows=None):
     dx2, _ = K.rmsnorm_bwd(x2, blk.norm2.weight, rstd2, dh2, dres=dx3, dw_out=gview, dw_accumulate=gacc)
     if rows is not None:  # the FFN half ran on the kept rows: the others receive no gradient from it
         dx2 = _put_rows(dx2, rt.B, rt.S, rows)
-    # ---- attention half
-    # the softmax backward's row sums (delta) are the epilogue of the out-projection's dgrad when the shape allows
-    fused = K.dgrad_attn_delta(dx2, att.out_proj.weight, ctx, att_saved[4], rt.B, rt.S, att.num_heads, att.head_dim)
-    dctx, delta = fused if fused is not None else (K.dgrad(dx2, att.out_proj.weight), None)
-    _wgrad(arena, att.out_proj.weight, None, dx2, ctx, wg)
-    dh1 = attention_backward(att, arena, h1, ctx, att_saved, dctx, rt, wg, delta)
-    gview, gacc = _vecgrad(arena, blk.norm1.weight)
-    dx, _ = K.rmsnorm_bwd(x, blk.norm1.weight, rstd1, dh1, dres=dx2, dw_out=gview, dw_accumulate=gacc)
+    dx = attention_half_backward(blk, arena, x, (h1, rstd1, ctx, att_saved), dx2, rt, wg)
     _flush_wgrads(wg)
     hook = getattr(blk, "_grad_ready", None)
     if hook is not None:

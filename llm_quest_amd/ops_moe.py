@@ -1,0 +1,215 @@
+"""Autograd layer of the Qwen3 mixture-of-experts path: the layer (``Qwen3MoE``) and the block (``MoETransformerBlock``) as ONE node each.
+
+The matrix products run on the existing GEMM launchers, one call per product for every expert that received tokens, on that expert's row
+segment of the expert-sorted buffers; everything else -- router, token-to-expert plan, row dispatch, weighted combine, their backwards -- is
+``csrc/moe.hip`` (launchers ``kernels_moe.py``).  The host reads the ``E`` counts once per layer and forward (the per-expert calls need the
+segment lengths); the backward reuses the numbers.  Nothing else in the layer synchronises.  A device-side segmented GEMM removes that read and
+the per-expert launches; it is the follow-up.
+"""
+
+import torch
+
+from . import _lib as L
+from . import kernels as K
+from . import kernels_moe as KM
+from . import ops
+
+BF16, F32 = torch.bfloat16, torch.float32
+
+
+# ----------------------------------------------------------------------------------------------- the layer
+def _gate_input(moe, h, gate_probas):
+    """The router's input: the gate's logits [T, E] (a column slice of a buffer whose pitch is a multiple of 8), or the replayed probabilities
+    (qwen3_moe.py:115-118: cast to the activations' dtype, a constant)."""
+    T, E = h.shape[0], moe.num_experts
+    if gate_probas is None:
+        buf = torch.empty((T, (E + 7) // 8 * 8), dtype=BF16, device=h.device)
+        return K.gemm(L.GEMM_NT, h, moe.gate.weight, out=buf[:, :E]), False
+    if gate_probas.dim() != 2:
+        raise ValueError("gate_probas must be 2D shaped as (batch*seq, num_experts)")
+    if tuple(gate_probas.shape) != (T, E):
+        raise ValueError(f"gate_probas must be (batch*seq, num_experts) = {(T, E)}, got {tuple(gate_probas.shape)}")
+    gp = gate_probas.detach()
+    if gp.device != h.device:
+        gp = gp.to(h.device)
+    L.require_gpu(gp)
+    return K.cast(gp.contiguous(), BF16), True
+
+
+def moe_forward(moe, arena, h, residual, gate_probas, keep):
+    """h bf16 [T, d] contiguous -> (residual + moe(h) [T, d], load loss fp32 [1] or None, the probabilities routed by, saved or None)."""
+    E, k, F_ = moe.num_experts, moe.top_k, moe.experts[0].hidden_dim
+    T, d = h.shape
+    gate_in, replay = _gate_input(moe, h, gate_probas)
+    p, idx, w, s = KM.route_fwd(gate_in, k, replay)
+    psum = K.colsum(p) if moe.training else None
+    counts, _, slot, row_token, loss = KM.plan(idx, E, psum, moe.load_coeff)
+    n_rows = counts.tolist()  # the layer's ONE device-to-host read: the per-expert launches need the segment lengths
+    align = KM.row_align()
+    xs = KM.gather_rows(h, row_token)
+    y = torch.empty_like(xs)  # rows no expert writes (padding) are never read: the combine kernels go through slot / row_token
+    fused = ops.FUSE_SWIGLU_FWD and F_ % 32 == 0
+    segs, gus, acts, off = [], [], [], 0
+    for e, n in enumerate(n_rows):
+        segs.append((off, n))
+        if n == 0:
+            gus.append(None)
+            acts.append(None)
+            continue
+        ex = moe.experts[e]
+        wgu = arena.fused(ex.lin1.weight, ex.lin_gate.weight)
+        if fused:  # the activation is the projection's epilogue (gu is still written: the backward needs it)
+            gu, a = K.gemm_gateup_swiglu(xs[off : off + n], wgu)
+        else:
+            gu = K.gemm(L.GEMM_NT, xs[off : off + n], wgu)
+            a = K.swiglu_fwd(gu, F_)
+        K.gemm(L.GEMM_NT, a, ex.lin2.weight, out=y[off : off + n])
+        gus.append(gu)
+        acts.append(a)
+        off += (n + align - 1) // align * align
+    out = KM.combine_fwd(y, slot, w, residual)
+    saved = (h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, replay) if keep else None
+    return out, loss, p, saved
+
+
+def moe_backward(moe, arena, saved, dout, g_loss, wg):
+    """d(h) [T, d] of ``moe_forward`` (the residual's share is the caller's).  ``g_loss``: dL/d(load loss), fp32 [1] on the device, or None.
+    Weight gradients are recorded in ``wg`` for the caller's grouped launches."""
+    h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, replay = saved
+    F_ = moe.experts[0].hidden_dim
+    dy, dw = KM.combine_bwd(dout, row_token, slot, w, None if replay else y)
+    dxs = torch.empty_like(xs)  # as y: only the rows in use are read back
+    for e, (off, n) in enumerate(segs):
+        ex = moe.experts[e]
+        if n == 0:  # no token: a defined, exactly zero gradient (upstream leaves None; the optimizer and the gradient sync need the buffer)
+            for first, last in ((ex.lin1.weight, ex.lin_gate.weight), (ex.lin2.weight, None)):
+                if first.requires_grad:
+                    view, acc = arena.grad_target(first, last)
+                    if not acc:
+                        view.zero_()
+            continue
+        dy_e, gu, a = dy[off : off + n], gus[e], acts[e]
+        if ops.FUSE_SWIGLU_BWD:  # the activation's backward is the dgrad GEMM's epilogue
+            dgu = K.gemm_dgrad_swiglu_bwd(dy_e, ex.lin2.weight, gu)
+        else:
+            dgu = K.swiglu_bwd(gu, K.dgrad(dy_e, ex.lin2.weight), F_)
+        ops._wgrad(arena, ex.lin2.weight, None, dy_e, a, wg)
+        K.dgrad(dgu, arena.fused(ex.lin1.weight, ex.lin_gate.weight), out=dxs[off : off + n])
+        ops._wgrad(arena, ex.lin1.weight, ex.lin_gate.weight, dgu, xs[off : off + n], wg)
+    dh = KM.combine_fwd(dxs, slot)  # the gather's backward: dh[t] = sum_j dxs[slot[t, j]]
+    if not replay:  # a replayed routing is a constant: the gate is not evaluated and gets no gradient
+        dlogits = KM.route_bwd(dw, w, s, idx, p, counts, g_loss, moe.load_coeff)
+        K.gemm(L.GEMM_NN, dlogits, moe.gate.weight, out=dh, residual=dh)
+        ops._wgrad(arena, moe.gate.weight, None, dlogits, h, wg)
+    return dh
+
+
+def _loss_grad(g):
+    """The incoming gradient of the load loss (0-dim, the activations' dtype) as the fp32 device scalar the route backward reads."""
+    return None if g is None else K.cast(g.reshape(1).contiguous(), F32)
+
+
+def _loss_out(loss, dtype):
+    return None if loss is None else K.cast(loss, dtype).reshape(())
+
+
+class MoEFn(torch.autograd.Function):
+    """``Qwen3MoE.forward`` on [..., d] bf16: returns (out, load loss or None, probabilities [T, E])."""
+
+    @staticmethod
+    def forward(ctx, x, moe, keep, gate_probas, *params):
+        arena = ops.arena_for(moe)
+        shp = x.shape
+        h = x.reshape(-1, shp[-1])
+        h = h if h.is_contiguous() else h.contiguous()
+        out, loss, p, saved = moe_forward(moe, arena, h, None, gate_probas, keep)
+        ctx.moe, ctx.saved, ctx.shp = moe, saved, shp
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(p)
+        return out.view(shp), _loss_out(loss, x.dtype), p
+
+    @staticmethod
+    def backward(ctx, dout, g_loss, _g_p):
+        moe, saved = ctx.moe, ctx.saved
+        if saved is None:
+            raise RuntimeError("MoEFn: backward through a forward that ran without grad mode")
+        h = saved[0]
+        dout2 = torch.zeros_like(h) if dout is None else dout.reshape(h.shape)
+        dout2 = dout2 if dout2.is_contiguous() else dout2.contiguous()
+        wg = []
+        dh = moe_backward(moe, ops.arena_for(moe), saved, dout2, _loss_grad(g_loss), wg)
+        ops._flush_wgrads(wg)
+        ctx.saved = None
+        return (dh.view(ctx.shp), None, None, None) + (None,) * len(moe._param_list)
+
+
+def run_moe(moe, x, gate_probas=None):
+    if not hasattr(moe, "_param_list"):
+        object.__setattr__(moe, "_param_list", list(moe.parameters()))
+    L.require_gpu(x)
+    if x.dtype != BF16:
+        raise TypeError(f"Qwen3MoE expects bf16 activations, got {x.dtype}")
+    return MoEFn.apply(x, moe, torch.is_grad_enabled(), gate_probas, *moe._param_list)
+
+
+# ----------------------------------------------------------------------------------------------- the block
+def block_forward(blk, x, rt, keep, gate_probas):
+    """The dense block's attention half (ops.attention_half_forward), then norm2 and the MoE layer with the residual add on the combine."""
+    arena = ops.arena_for(blk)
+    x2, att_saved = ops.attention_half_forward(blk, arena, x, rt)
+    h2, rstd2 = K.rmsnorm_fwd(x2, blk.norm2.weight)
+    x3, loss, p, moe_saved = moe_forward(blk.moe, arena, h2, x2, gate_probas, keep)
+    saved = (x, att_saved, x2, rstd2, moe_saved) if keep else None
+    return x3, loss, p, saved
+
+
+def block_backward(blk, saved, dx3, g_loss, rt):
+    arena = ops.arena_for(blk)
+    x, att_saved, x2, rstd2, moe_saved = saved
+    wg = []  # the weight gradients run as grouped launches at the end (their operands stay alive until then)
+    # ---- MoE half
+    dh2 = moe_backward(blk.moe, arena, moe_saved, dx3, g_loss, wg)
+    gview, gacc = ops._vecgrad(arena, blk.norm2.weight)
+    dx2, _ = K.rmsnorm_bwd(x2, blk.norm2.weight, rstd2, dh2, dres=dx3, dw_out=gview, dw_accumulate=gacc)
+    dx = ops.attention_half_backward(blk, arena, x, att_saved, dx2, rt, wg)
+    ops._flush_wgrads(wg)
+    hook = getattr(blk, "_grad_ready", None)
+    if hook is not None:
+        hook(blk)
+    return dx
+
+
+class MoEBlockFn(torch.autograd.Function):
+    """``MoETransformerBlock.forward`` as one node: returns (y, load loss or None, probabilities [T, E])."""
+
+    @staticmethod
+    def forward(ctx, x, blk, rt, keep, gate_probas, *params):
+        B, S, d = x.shape
+        x2 = x.reshape(B * S, d)
+        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        y, loss, p, saved = block_forward(blk, x2, rt, keep, gate_probas)
+        ctx.blk, ctx.rt, ctx.saved, ctx.shape = blk, rt, saved, (B, S, d)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(p)
+        return y.view(B, S, d), _loss_out(loss, x.dtype), p
+
+    @staticmethod
+    def backward(ctx, dy, g_loss, _g_p):
+        B, S, d = ctx.shape
+        saved = ctx.saved
+        if saved is None:
+            raise RuntimeError("MoEBlockFn: backward through a forward that ran without grad mode")
+        dy2 = torch.zeros_like(saved[0]) if dy is None else dy.reshape(-1, d)
+        dy2 = dy2 if dy2.is_contiguous() else dy2.contiguous()
+        dx = block_backward(ctx.blk, saved, dy2, _loss_grad(g_loss), ctx.rt)
+        ctx.saved = None
+        return (dx.view(B, S, d), None, None, None, None) + (None,) * len(ctx.blk._param_list)
+
+
+def run_block(blk, x, rt, gate_probas=None):
+    if not hasattr(blk, "_param_list"):
+        object.__setattr__(blk, "_param_list", list(blk.parameters()))
+    L.require_gpu(x)
+    if x.dtype != BF16:
+        raise TypeError(f"Qwen3 MoE block expects bf16 activations, got {x.dtype}")
+    return MoEBlockFn.apply(x, blk, rt, torch.is_grad_enabled(), gate_probas, *blk._param_list)

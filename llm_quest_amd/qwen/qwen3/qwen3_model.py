@@ -1,4 +1,4 @@
-"""Dense Qwen3 model on HIP kernels -- API of ``llm_quest/qwen/qwen3/qwen3_model.py`` (Qwen3Model).
+"""Qwen3 models on HIP kernels -- API of ``llm_quest/qwen/qwen3/qwen3_model.py`` (Qwen3Model, dense; Qwen3MoEModel, mixture of experts).
 
 Extensions over the reference signature (both needed by BASELINE config 4):
   * ``forward(..., input_embedded=False)``: ``x`` may already be embeddings (b, s, emb) -- the early-fusion entry that
@@ -15,7 +15,7 @@ from llm_quest_amd import ops
 from llm_quest_amd.arena import ParamArena
 from llm_quest_amd.common.buffers import GlobalBuffers
 from llm_quest_amd.qwen.qwen3.qwen3_attention import PytorchRMSNorm
-from llm_quest_amd.qwen.qwen3.qwen3_transformer_block import TransformerBlock
+from llm_quest_amd.qwen.qwen3.qwen3_transformer_block import MoETransformerBlock, TransformerBlock
 
 
 class _Embedding(nn.Embedding):
@@ -37,12 +37,14 @@ class _OutHead(nn.Module):
 
 
 class Qwen3Model(nn.Module):
+    _block_class = TransformerBlock
+
     def __init__(self, cfg):
         super().__init__()
         self.tie_embeddings = cfg["tie_embeddings"]
         self.gradient_checkpointing = cfg.get("gradient_checkpointing", False)
         self.emb_dict = _Embedding(cfg["vocab_size"], cfg["emb_dim"], dtype=cfg["dtype"])
-        self.trf_blocks = nn.ModuleList([TransformerBlock(cfg, i) for i in range(cfg["n_layers"])])
+        self.trf_blocks = nn.ModuleList([self._block_class(cfg, i) for i in range(cfg["n_layers"])])
         self.final_norm = PytorchRMSNorm(cfg["emb_dim"], dtype=cfg["dtype"])
         if self.tie_embeddings:
             # shared matrix re-initialised Xavier-uniform, as upstream does for pre-training (qwen3_model.py:36-45)
@@ -121,3 +123,45 @@ class Qwen3Model(nn.Module):
         h = hidden_rows if hidden_rows.is_contiguous() else hidden_rows.contiguous()
         t = targets.reshape(-1).contiguous()
         return ops.LMHeadLossFn.apply(h, t, self.out_head, self.out_head.weight, torch.is_grad_enabled())
+
+
+class Qwen3MoEModel(Qwen3Model):
+    """Mixture-of-experts variant of Qwen3Model with gate / routing replay (reference: qwen3_model.py:97-179).  bf16 training path and no-grad
+    forward; the KV-cache path and gradient checkpointing are refused.  The blocks' auxiliary losses stay on ``blk.moe.moe_loss``."""
+
+    _block_class = MoETransformerBlock
+
+    def __init__(self, cfg):
+        if cfg.get("gradient_checkpointing", False):
+            raise NotImplementedError("Qwen3MoEModel: gradient_checkpointing=True is not built for mixture-of-experts blocks")
+        super().__init__(cfg)  # the dense model's construction with MoE blocks (upstream builds the dense blocks first and swaps them)
+
+    def forward(self, x, attn_mask=None, kv_cache=None, position_ids=None, gate_probas=None, return_gate_probas=False):
+        """Logits (b, s, vocab); with ``return_gate_probas`` also the list of every layer's (b*s, num_experts) gate probabilities.
+        ``gate_probas``: one tensor for all layers, or a list / tuple with one entry per layer (routing replay)."""
+        if kv_cache is not None:
+            raise NotImplementedError("Qwen3MoEModel: the KV-cache path (kv_cache is not None) is not built for mixture-of-experts blocks")
+        if self.gradient_checkpointing:
+            raise NotImplementedError("Qwen3MoEModel: gradient_checkpointing=True is not built for mixture-of-experts blocks")
+        self._build_arenas()
+        L.require_gpu(x)
+        x = self.emb_dict(x)
+        B, S, _ = x.shape
+        rt = ops.make_runtime(B, S, x.device, self.cos, self.sin, attn_mask, position_ids)
+        collected = []
+        for i, blk in enumerate(self.trf_blocks):
+            current = None
+            if gate_probas is not None:
+                if isinstance(gate_probas, (list, tuple)):
+                    if i < len(gate_probas):
+                        current = gate_probas[i]
+                else:
+                    current = gate_probas
+            out = blk(x, self.mask, self.cos, self.sin, attn_mask, None, position_ids, current, return_gate_probas, _runtime=rt)
+            if return_gate_probas:
+                x, layer_probas = out
+                collected.append(layer_probas)
+            else:
+                x = out
+        logits = self.out_head(self.final_norm(x))
+        return (logits, collected) if return_gate_probas else logits

@@ -1,11 +1,12 @@
-"""Qwen3 SwiGLU FFN and transformer block -- API of ``llm_quest/qwen/qwen3/qwen3_transformer_block.py``."""
+"""Qwen3 SwiGLU FFN, transformer block and mixture-of-experts block -- API of ``llm_quest/qwen/qwen3/qwen3_transformer_block.py``."""
 
 import torch
 import torch.nn as nn
 
 from llm_quest_amd import _lib as L
 from llm_quest_amd import kernels as K
-from llm_quest_amd import ops
+from llm_quest_amd import ops, ops_moe
+from llm_quest_amd.moe.qwen3_moe import Qwen3MoE
 from llm_quest_amd.qwen.qwen3.qwen3_attention import GroupedQueryAttention, PytorchRMSNorm
 
 
@@ -86,3 +87,34 @@ class TransformerBlock(nn.Module):
             return (y if y.dtype == x.dtype else K.cast(y, x.dtype)).view(B, S, -1)
         rt = _runtime if _runtime is not None else ops.make_runtime(B, S, x.device, cos, sin, attn_mask, position_ids)
         return ops.run_block(self, x, rt)
+
+
+class MoETransformerBlock(nn.Module):
+    """The dense block with a mixture of experts in place of the FFN (reference: qwen3_transformer_block.py:106-153).
+
+    Runs as ONE autograd node (ops_moe.MoEBlockFn): the attention half is the dense block's launches, the MoE half's residual add rides on
+    the combine kernel.  The layer is named ``moe``, as upstream, so ``engine.global_loss`` (which collects ``ffn.moe_loss``) does not add its
+    auxiliary loss; a caller that wants it adds ``blk.moe.moe_loss`` to the loss itself.
+    """
+
+    def __init__(self, cfg, layer_idx):
+        super().__init__()
+        self.att = GroupedQueryAttention(
+            d_in=cfg["emb_dim"], num_heads=cfg["n_heads"], num_kv_groups=cfg["num_kv_groups"], head_dim=cfg["head_dim"],
+            dtype=cfg["dtype"], layer_idx=layer_idx,
+        )
+        self.norm1 = PytorchRMSNorm(cfg["emb_dim"], dtype=cfg["dtype"])
+        self.norm2 = PytorchRMSNorm(cfg["emb_dim"], dtype=cfg["dtype"])
+        self.moe = Qwen3MoE(cfg=cfg)
+
+    def forward(self, x, mask, cos, sin, attn_mask=None, kv_cache=None, position_ids=None, gate_probas=None, return_gate_probas=False, _runtime=None):
+        if kv_cache is not None:
+            raise NotImplementedError("MoETransformerBlock: the KV-cache path (kv_cache is not None) is not built for mixture-of-experts blocks")
+        if gate_probas is not None and gate_probas.dim() != 2:
+            raise ValueError("gate_probas must be 2D shaped as (batch*seq, num_experts)")
+        B, S, _ = x.shape
+        rt = _runtime if _runtime is not None else ops.make_runtime(B, S, x.device, cos, sin, attn_mask, position_ids)
+        y, loss, probas = ops_moe.run_block(self, x, rt, gate_probas)
+        if self.moe.training:
+            self.moe.moe_loss = loss
+        return (y, probas) if return_gate_probas else y
