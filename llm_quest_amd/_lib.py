@@ -135,6 +135,13 @@ SIGNATURES = {
     "mi355_moe_gather_rows": [_L, _L, _I, _P, _P, _L, _P, _L, _P],
     "mi355_moe_combine_fwd": [_L, _L, _I, _I, _P, _P, _P, _L, _P, _L, _P, _L, _P],
     "mi355_moe_combine_bwd": [_L, _L, _I, _I, _P, _P, _P, _P, _L, _P, _L, _P, _L, _P, _P],
+    # DeepSeekMoE: bias-balanced router, bias update, the shared experts' bias + SiLU, combine with the shared output (csrc/deepseek_moe.hip)
+    "mi355_dsmoe_route_fwd": [_L, _I, _I, _P, _L, _P, _I, _P, _P, _L, _P, _P, _P, _P],
+    "mi355_dsmoe_bias_update": [_I, _P, _P, _I, _F, _P, _P],
+    "mi355_dsmoe_bias_silu_fwd": [_L, _I, _P, _L, _P, _P, _L, _P],
+    "mi355_dsmoe_bias_silu_bwd": [_L, _I, _P, _L, _P, _L, _P, _L, _P],
+    "mi355_dsmoe_combine_fwd": [_L, _L, _I, _I, _P, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P],
+    "mi355_dsmoe_colsum_parts": [_L, _I, _P, _L, _P, _I, _P],
 }
 # size / constant queries: no stream argument, the return value is the answer (name -> (argtypes, restype))
 QUERIES = {

@@ -1,7 +1,7 @@
-"""DeepSeek-V3 dense model with Multi-Token-Prediction modules on HIP kernels -- API of
+"""DeepSeek-V3 model with Multi-Token-Prediction modules on HIP kernels -- API of
 ``llm_quest/llama3_to_deepseekv3/deepseek_model.py`` (MTPModule, MainModel, DeepSeekV3Model), bf16 training path.
 
-Every block is the dense one (``layer < cfg["num_ffn"]``); a config that asks for a DeepSeekMoE layer is refused by ``TransformerBlock``.
+Blocks ``layer < cfg["num_ffn"]`` are dense, the rest hold a ``DeepSeekMoE`` (their config keys are checked there); the MTP blocks are dense.
 Extensions over the reference signatures: ``MainModel.forward_hidden`` (final-normed hidden states and the block output, the head not yet
 applied: the loss runs the head and the cross entropy as one node) and ``DeepSeekV3Model.arenas()``.
 """
@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from llm_quest_amd import _lib as L
-from llm_quest_amd import ops, ops_mla
+from llm_quest_amd import ops, ops_dsmoe, ops_mla
 from llm_quest_amd.arena import ParamArena
 from llm_quest_amd.common.buffers import GlobalBuffers
 from llm_quest_amd.llama3_to_deepseekv3.deepseek_transformer_block import RMSNorm, TransformerBlock
@@ -85,7 +85,7 @@ class MTPModule(nn.Module):
 
 
 class MainModel(nn.Module):
-    """Embedding, the dense blocks, final norm and head; returns (logits, h_curr) with h_curr the last block's output (deepseek_model.py:52-82)."""
+    """Embedding, the blocks, final norm and head; returns (logits, h_curr) with h_curr the last block's output (deepseek_model.py:52-82)."""
 
     def __init__(self, cfg):
         super().__init__()
@@ -106,7 +106,7 @@ class MainModel(nn.Module):
         if self._arenas_built:
             return
         for blk in self.trf_blocks:
-            ar = ParamArena(list(blk.named_parameters()))
+            ar = ParamArena(ops_dsmoe.arena_named_params(blk))  # a routed expert's lin_gate in front of its lin1; dense blocks unchanged
             for m in blk.modules():
                 object.__setattr__(m, "_arena", ar)
         ar = ParamArena([("emb_layer.weight", self.emb_layer.weight), ("final_norm.scale", self.final_norm.scale), ("out_layer.weight", self.out_layer.weight)])

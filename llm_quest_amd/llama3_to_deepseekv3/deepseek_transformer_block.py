@@ -1,11 +1,12 @@
 """DeepSeek-V3 RMSNorm, SiLU, SwiGLU FFN and the dense transformer block -- API of
-``llm_quest/llama3_to_deepseekv3/deepseek_transformer_block.py``.  The Mixture-of-Experts layers (``layer >= cfg["num_ffn"]``) are not built."""
+``llm_quest/llama3_to_deepseekv3/deepseek_transformer_block.py``.  Layers ``layer >= cfg["num_ffn"]`` hold a ``DeepSeekMoE`` (``moe/deepseek_moe.py``)."""
 
 import torch
 import torch.nn as nn
 
-from llm_quest_amd import ops_g3, ops_mla
+from llm_quest_amd import ops_dsmoe, ops_g3, ops_mla
 from llm_quest_amd.llama3_to_deepseekv3.deepseek_attention import MultiLatentAttention, RMSNorm  # noqa: F401  (RMSNorm: same class upstream defines here)
+from llm_quest_amd.moe.deepseek_moe import DeepSeekMoE
 
 
 class SiLU(nn.Module):
@@ -37,17 +38,14 @@ class FFN(nn.Module):
 
 
 class TransformerBlock(nn.Module):
-    """x + att(norm_1(x)); x + ffn(norm_2(x)) (deepseek_transformer_block.py:110-155), the dense form: ``layer < cfg["num_ffn"]``.
+    """x + att(norm_1(x)); x + ffn(norm_2(x)) (deepseek_transformer_block.py:110-155): ``ffn`` is the dense ``FFN`` for ``layer < cfg["num_ffn"]`` and a
+    ``DeepSeekMoE`` from there on (a config without the MoE keys is refused there with ``NotImplementedError``).
 
-    Runs as ONE autograd node (ops_mla.DeepSeekBlockFn); the residual adds ride on the out-projection and lin2 GEMMs."""
+    Runs as ONE autograd node (ops_mla.DeepSeekBlockFn / ops_dsmoe.DeepSeekMoEBlockFn); the residual adds ride on the out-projection and on the lin2
+    GEMM, resp. the MoE combine."""
 
     def __init__(self, cfg, layer):
         super().__init__()
-        if layer >= cfg["num_ffn"]:
-            raise NotImplementedError(
-                f"TransformerBlock(layer={layer}) with num_ffn={cfg['num_ffn']} is a DeepSeekMoE layer, which is out of scope here: only the dense "
-                f"blocks (layer < num_ffn) are built"
-            )
         self.att = MultiLatentAttention(
             d_in=cfg["emb_dim"],
             d_out=cfg["emb_dim"],
@@ -55,10 +53,12 @@ class TransformerBlock(nn.Module):
         )
         self.norm_1 = RMSNorm(cfg["emb_dim"])
         self.norm_2 = RMSNorm(cfg["emb_dim"])
-        self.ffn = FFN(cfg)
+        self.ffn = FFN(cfg) if layer < cfg["num_ffn"] else DeepSeekMoE(cfg)
 
     def forward(self, x, mask, cos, sin, _runtime=None):
         B, S, _ = x.shape
         ops_mla.check_mask(mask, S)
         rt = _runtime if _runtime is not None else ops_mla.make_runtime(self, B, S, cos, sin)
+        if isinstance(self.ffn, DeepSeekMoE):
+            return ops_dsmoe.run_block(self, x, rt)
         return ops_mla.run_block(self, x, rt)
