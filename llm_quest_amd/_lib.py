@@ -27,6 +27,8 @@ _P, _I, _L, _F, _U = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_uint64
 SIGNATURES = {
     "mi355_gemm_bf16": [_I, _L, _L, _L, _P, _L, _P, _L, _P, _L, _I, _P, _P, _L, _I, _P, _L, _I, _P],
     "mi355_gemm_bf16_grouped": [_I, _I, _P, _I, _I, _P],
+    "mi355_gemm_bf16_segmented": [_I, _I, _P, _P, _L, _L, _L, _L, _P, _L, _P, _L, _L, _P, _L, _P, _L, _I, _I, _P],
+    "mi355_gemm_bf16_segmented_tn": [_I, _P, _P, _L, _L, _L, _P, _L, _P, _L, _P, _L, _L, _I, _P, _L, _I, _P],
     "mi355_gemm_bf16_attn_delta": [_L, _L, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P],
     "mi355_adamw": [_L, _P, _I, _P, _I, _P, _P, _F, _F, _F, _F, _F, _I, _P, _F, _P],
     "mi355_colsum": [_L, _L, _P, _I, _L, _P, _I, _P],

@@ -8,7 +8,8 @@
 //   combine   out[t] = residual[t] + sum_j w[t, j] * Y[slot[t, j]]   (j ascending, fp32, one rounding) -- also the gather's backward with w = NULL
 //   and the backwards of combine and route.
 //
-// The expert products themselves run on the existing GEMM entry points, one call per expert that received tokens, on its row segment.
+// The expert products themselves run as segmented GEMMs (gemm_segmented.hip: mi355_gemm_bf16_segmented / _segmented_tn), one launch per product over all experts, on the
+// row segments this plan leaves in device memory (counts, offsets); nothing here is read back by the host.
 //
 // No atomics and no workgroup that waits for another: the sort is three launches (per-chunk ranks and histograms, ONE workgroup for the scan over
 // chunks and experts, the scatter), every output element has exactly one writer, every sum a fixed order -- two runs give the same bits.

@@ -223,6 +223,115 @@ def gemm_grouped(form, problems, tile=0):
     L.call("mi355_gemm_bf16_grouped", form, len(problems), _c.cast(table, _c.c_void_p), L.dt_code(odt), tile or _TILE_BY_FORM[form] or (_TILE_OVERRIDE if _TILE_OVERRIDE in (1, 3, 4, 5) else 0))
 
 
+MAX_SEGMENTS = 128  # csrc/gemm_segmented.hip: MAX_SEG
+
+
+def expert_stack(views):
+    """The per-expert 2-D views (one shape, one pitch, unit inner stride) as ONE 3-D view [E, rows, cols] whose stride(0) is the distance between two
+    experts.  Raises unless the views lie at one constant, non-overlapping stride in one storage -- what a ``ParamArena`` gives consecutive experts."""
+    v0 = views[0]
+    E = len(views)
+    if not 1 <= E <= MAX_SEGMENTS:
+        raise ValueError(f"expert_stack: 1..{MAX_SEGMENTS} experts, got {E}")
+    if v0.dim() != 2 or v0.stride(1) != 1:
+        raise ValueError("expert_stack: the per-expert operands must be 2-D with unit inner stride")
+    rows, cols = v0.shape
+    esz = v0.element_size()
+    step = (views[1].data_ptr() - v0.data_ptr()) if E > 1 else rows * v0.stride(0) * esz
+    if step % esz or step // esz < (rows - 1) * v0.stride(0) + cols:
+        raise RuntimeError("expert_stack: the experts' operands overlap or are not laid out in ascending order")
+    for e, v in enumerate(views):
+        if v.dtype != v0.dtype or v.device != v0.device or tuple(v.shape) != (rows, cols) or v.stride() != v0.stride() or v.data_ptr() - v0.data_ptr() != e * step:
+            raise RuntimeError(f"expert_stack: expert {e}'s operand does not lie at the uniform stride of {step // esz} elements (the arena does not provide it)")
+    return v0.as_strided((E, rows, cols), (step // esz, v0.stride(0), 1))
+
+
+def _check_stack(t, name, dtypes=(BF16,)):
+    if t.dim() != 3 or t.stride(2) != 1 or t.dtype not in dtypes or not 1 <= t.shape[0] <= MAX_SEGMENTS:
+        raise ValueError(f"{name} must be a 3-D expert stack [E <= {MAX_SEGMENTS}, rows, cols] with unit inner stride (see expert_stack), got {t.dtype} {tuple(t.shape)} {t.stride()}")
+    E, rows, cols = t.shape
+    if t.stride(1) % 8 or t.stride(1) < cols or t.stride(0) % 8 or (E > 1 and t.stride(0) < (rows - 1) * t.stride(1) + cols) or t.data_ptr() % 16:
+        raise ValueError(f"{name}: pitch and expert stride must be multiples of 8 elements, experts must not overlap, the base must be 16-byte aligned; got strides {t.stride()}")
+
+
+def _check_seg_table(counts, offsets, E):
+    I32 = torch.int32
+    if counts.dtype != I32 or offsets.dtype != I32 or not counts.is_contiguous() or not offsets.is_contiguous() or counts.numel() != E or offsets.numel() < E:
+        raise ValueError(f"segmented gemm: counts must be contiguous int32 [{E}] and offsets contiguous int32 [>= {E}]")
+
+
+def _check_seg_rows(t, name, R, width=None):
+    if t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != R or (width is not None and t.shape[1] != width):
+        raise ValueError(f"segmented gemm: {name} must be bf16 [{R}, {width if width is not None else '*'}] with unit inner stride, got {t.dtype} {tuple(t.shape)} {t.stride()}")
+    if t.shape[1] % 8 or t.stride(0) % 8 or t.stride(0) < t.shape[1] or t.data_ptr() % 16:
+        raise ValueError(f"segmented gemm: {name}: width {t.shape[1]} and pitch {t.stride(0)} must be multiples of 8 (pitch >= width), the base 16-byte aligned")
+
+
+def gemm_segmented(form, a, b, counts, offsets, max_rows, out=None, epilogue=None, second=None, residual=None, tile=0):
+    """The products of all experts of a MoE layer in ONE launch, no host read: segment e = rows offsets[e] .. + counts[e] of ``a`` bf16 [R, K] times
+    expert e of the stack ``b`` ([E, N, K] for NT, [E, K, N] for NN; ``expert_stack``).  ``counts`` / ``offsets`` are ``kernels_moe.plan``'s device
+    tensors, ``max_rows`` = tokens * top_k bounds the sum of the counts.  Rows outside the segments are neither read nor written.
+      epilogue None          returns C [R, N] (+ ``residual`` [R, N])
+      epilogue 'swiglu_fwd'  NT, N = 2F, F % 32 == 0: returns (gu [R, 2F], a [R, F])                       (``gemm_gateup_swiglu`` per segment)
+      epilogue 'swiglu_bwd'  NN, N = F; ``second`` = the forward's gu [R, 2F]: returns d(gate-up) [R, 2F]  (``gemm_dgrad_swiglu_bwd`` per segment)
+    Bit-identical per segment to the per-expert launchers on the 128x128 tile."""
+    L.require_gpu(a, b, counts, offsets, out, second, residual)
+    if form not in (L.GEMM_NT, L.GEMM_NN):
+        raise ValueError("gemm_segmented: form must be NT or NN (the TN form is gemm_segmented_wgrad)")
+    if a.dim() != 2:
+        raise ValueError("gemm_segmented: A must be 2-D [R, K]")
+    R, Kd = a.shape
+    _check_seg_rows(a, "A", R)
+    _check_stack(b, "gemm_segmented: B")
+    E = b.shape[0]
+    N, K2 = (b.shape[1], b.shape[2]) if form == L.GEMM_NT else (b.shape[2], b.shape[1])
+    if K2 != Kd or N % 8:
+        raise ValueError(f"gemm_segmented: inner dimensions differ ({Kd} vs {K2}) or N = {N} is no multiple of 8")
+    _check_seg_table(counts, offsets, E)
+    if not 0 <= max_rows <= R:
+        raise ValueError(f"gemm_segmented: max_rows = {max_rows} must lie in 0..R = {R}")
+    epi, slot, width = L.EPI_NONE, residual, N
+    if epilogue == "swiglu_fwd":
+        if form != L.GEMM_NT or N % 64 or residual is not None or out is not None:
+            raise ValueError("gemm_segmented(swiglu_fwd): NT form, fused weight [E, 2F, K] with F % 32 == 0, no residual, no preallocated output")
+        epi, slot = L.EPI_SWIGLU_FWD, torch.empty((R, N // 2), dtype=BF16, device=a.device)
+    elif epilogue == "swiglu_bwd":
+        if form != L.GEMM_NN or second is None or residual is not None or out is not None:
+            raise ValueError("gemm_segmented(swiglu_bwd): NN form, `second` = the forward's gate-up output, no residual, no preallocated output")
+        _check_seg_rows(second, "the gate-up output", R, 2 * N)
+        epi, slot, width = L.EPI_SWIGLU_BWD, second, 2 * N
+    elif epilogue is not None:
+        raise ValueError(f"gemm_segmented: unknown epilogue {epilogue!r}")
+    elif residual is not None:
+        _check_seg_rows(residual, "residual", R, N)
+    if out is None:
+        out = torch.empty((R, width), dtype=BF16, device=a.device)
+    _check_seg_rows(out, "C", R, width)
+    L.call("mi355_gemm_bf16_segmented", form, E, L.ptr(counts), L.ptr(offsets), max_rows, R, N, Kd, L.ptr(a), a.stride(0), L.ptr(b), b.stride(1), b.stride(0),
+           L.ptr(out), out.stride(0), L.ptr(slot), 0 if slot is None else slot.stride(0), epi, tile)
+    return (out, slot) if epi == L.EPI_SWIGLU_FWD else out
+
+
+def gemm_segmented_wgrad(dy, x, counts, offsets, out, accumulate=False, tile=0):
+    """The weight gradients of all experts in ONE launch: out[e] (+)= dy_seg^T x_seg with ``dy`` bf16 [R, M], ``x`` bf16 [R, N] and ``out`` the stack
+    [E, M, N] (bf16 or fp32; ``expert_stack`` over the gradient views).  An expert without a row ends with exactly zero, or keeps exactly its old value
+    under ``accumulate``.  Bit-identical per expert to ``gemm(GEMM_TN, ..., tile=1, allow_split_k=False)``."""
+    L.require_gpu(dy, x, counts, offsets, out)
+    if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0]:
+        raise ValueError("gemm_segmented_wgrad: dY [R, M] and X [R, N] must share their rows")
+    R = dy.shape[0]
+    _check_seg_rows(dy, "dY", R)
+    _check_seg_rows(x, "X", R)
+    _check_stack(out, "gemm_segmented_wgrad: out", (BF16, F32))
+    E, M, N = out.shape
+    if (M, N) != (dy.shape[1], x.shape[1]):
+        raise ValueError(f"gemm_segmented_wgrad: out must be [E, {dy.shape[1]}, {x.shape[1]}], got {tuple(out.shape)}")
+    _check_seg_table(counts, offsets, E)
+    L.call("mi355_gemm_bf16_segmented_tn", E, L.ptr(counts), L.ptr(offsets), R, M, N, L.ptr(dy), dy.stride(0), L.ptr(x), x.stride(0), L.ptr(out), out.stride(1),
+           out.stride(0), L.dt_code(out.dtype), L.ptr(out) if accumulate else None, out.stride(1) if accumulate else 0, tile)
+    return out
+
+
 # Measured (ViT-B/16 training step, B = 256, same box): fused 65.5 ms, separate kernels 64.1 ms -- erf / tanh in the epilogue sit on the tile's critical
 # path with one workgroup per CU, the separate kernels run HBM-bound over the whole chip.  So the separate form is the default; 1 selects the fused one.
 _FUSE_GELU = os.environ.get("MI355_FUSE_GELU", "0") != "0"

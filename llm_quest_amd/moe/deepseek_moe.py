@@ -3,7 +3,8 @@ max_violation_batch, max_violation_step).
 
 The layer runs as ONE autograd node (``ops_dsmoe.DeepSeekMoEFn``; inside the DeepSeek-V3 ``TransformerBlock`` the whole block is one): the
 bias-balanced router, the bias update, the shared experts' bias + SiLU and the combine are ``csrc/deepseek_moe.hip``; the token-to-expert plan, the
-row dispatch and the backwards of combine and router are ``csrc/moe.hip``; every product is an existing GEMM.  bf16 training path and no-grad
+row dispatch and the backwards of combine and router are ``csrc/moe.hip``; the routed experts' products are segmented GEMMs (``csrc/gemm_segmented.hip``: one launch per
+product over all routed experts, no host read), the gate's and the shared experts' the existing GEMMs.  bf16 training path and no-grad
 forward.  ``state_dict`` matches upstream key for key.
 
 Limits, checked in the constructor: 1..128 routed experts (any value), ``top_k`` at most 8, ``emb_dim`` and the scaled hidden size multiples of 8.

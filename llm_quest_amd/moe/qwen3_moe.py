@@ -1,8 +1,8 @@
 """Qwen3 mixture-of-experts layer on HIP kernels -- API of ``llm_quest/moe/qwen3_moe.py`` (router_weights_init, Expert, Qwen3MoE).
 
 The layer runs as ONE autograd node (``ops_moe.MoEFn``; inside ``MoETransformerBlock`` the whole block is one): the router, the
-token-to-expert plan, the row dispatch and the weighted combine are ``csrc/moe.hip``, the expert products the existing GEMMs, one call per
-product for every expert that received tokens.  bf16 training path and no-grad forward.
+token-to-expert plan, the row dispatch and the weighted combine are ``csrc/moe.hip``, the expert products segmented GEMMs (``csrc/gemm_segmented.hip``): one launch
+per product over all experts, the segment table read on the device -- no host read.  bf16 training path and no-grad forward.
 
 Differences from upstream, all refusals or definitions where upstream leaves a gap:
   * only SiLU experts; ``shared_expert_hidden_dim`` (the Qwen3-Next shared expert) raises ``NotImplementedError``;

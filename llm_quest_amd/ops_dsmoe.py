@@ -1,10 +1,12 @@
 """Autograd layer of the DeepSeekMoE path: the layer (``DeepSeekMoE``) and the DeepSeek-V3 block that holds one, as ONE node each.
 
-Same construction as ``ops_moe.py``: the routed experts' products run on the existing GEMM launchers, one call per product for every expert that
-received tokens, on that expert's row segment of the expert-sorted buffers; plan, row dispatch, combine backward and router backward are
-``csrc/moe.hip``; the bias-balanced router, the bias update, the shared experts' bias + SiLU, the combine that takes the shared output and the
-fixed-order column sums of the bias gradients are ``csrc/deepseek_moe.hip`` (launchers ``kernels_dsmoe.py``).  The host reads the routed experts'
-counts once per layer and forward.
+Same construction as ``ops_moe.py``, whose pieces it shares: the routed experts' products run as segmented GEMMs (``ops_moe.experts_forward`` /
+``experts_backward``: gate-up + SwiGLU, ``lin2``, the two dgrads and the two weight gradients are one launch each over all routed experts, the plan's
+``counts`` / ``offsets`` read on the device), so the layer's forward and backward contain no device-to-host read and their launch count does not grow with
+the number of experts; ``MI355_MOE_SEGMENTED=0`` keeps the per-expert path (one host read of the counts, two or three launches per expert).  Plan, row
+dispatch, combine backward and router backward are ``csrc/moe.hip``; the bias-balanced router, the bias update, the shared experts' bias + SiLU, the
+combine that takes the shared output and the fixed-order column sums of the bias gradients are ``csrc/deepseek_moe.hip`` (launchers
+``kernels_dsmoe.py``).
 
 Two layout points:
   * a routed expert is lin2(silu(lin1(x)) * lin_gate(x)): the SiLU sits on ``lin1``.  The fused gate-up kernels compute u * silu(g) on [u | g], so
@@ -23,7 +25,7 @@ from . import kernels as K
 from . import kernels_dsmoe as KD
 from . import kernels_g3 as KG
 from . import kernels_moe as KM
-from . import ops, ops_mla
+from . import ops, ops_mla, ops_moe
 from .arena import ParamArena
 from .ops_g3 import _add_vecgrad, _flat
 
@@ -126,20 +128,10 @@ def _flush(wg):
 
 
 # ----------------------------------------------------------------------------------------------- the layer
-def moe_forward(moe, arena, h, residual, keep):
-    """h bf16 [T, d] contiguous -> residual + shared(h) + routed(h) [T, d]; updates ``moe.biases`` and sets ``moe.max_vio`` on the device."""
-    E, k, F_ = moe.num_routed, moe.top_k, moe.routed_experts[0].hidden_dim
-    T, d = h.shape
-    wg8, bg8 = _gate_operands(moe)
-    logits = K.gemm(L.GEMM_NT, h, wg8, bias=bg8)  # bf16(h W^T + b): one rounding after the bias is in, as addmm
-    p, idx, w, s = KD.route_fwd(logits[:, :E], moe.biases, k, _forced(moe, T))
-    counts, _, slot, row_token, _ = KM.plan(idx, E)
-    max_vio = KD.bias_update(counts, moe.biases, moe.bias_update_rate)  # after this forward's router, on its stream
-    object.__setattr__(moe, "max_vio", max_vio.reshape(()))
-    object.__setattr__(moe, "_routed", (idx, counts))  # this forward's selection and counts, device tensors (tests and metrics; nothing here reads them back)
-    n_rows = counts.tolist()  # the layer's ONE device-to-host read: the per-expert launches need the segment lengths
+def _experts_forward_loop(moe, arena, xs, counts, F_):
+    """The per-expert path (``ops_moe.SEGMENTED`` off): the host reads the counts, then two or three launches per routed expert that received tokens."""
+    n_rows = counts.tolist()  # the device-to-host read the segmented path does without
     align = KM.row_align()
-    xs = KM.gather_rows(h, row_token)
     y = torch.empty_like(xs)  # padding rows are never read: the combine kernels go through slot / row_token
     fused = ops.FUSE_SWIGLU_FWD and F_ % 32 == 0
     segs, gus, acts, off = [], [], [], 0
@@ -160,20 +152,37 @@ def moe_forward(moe, arena, h, residual, keep):
         gus.append(gu)
         acts.append(a)
         off += (n + align - 1) // align * align
+    return y, gus, acts, segs
+
+
+def moe_forward(moe, arena, h, residual, keep):
+    """h bf16 [T, d] contiguous -> residual + shared(h) + routed(h) [T, d]; updates ``moe.biases`` and sets ``moe.max_vio`` on the device."""
+    E, k, F_ = moe.num_routed, moe.top_k, moe.routed_experts[0].hidden_dim
+    T, d = h.shape
+    wg8, bg8 = _gate_operands(moe)
+    logits = K.gemm(L.GEMM_NT, h, wg8, bias=bg8)  # bf16(h W^T + b): one rounding after the bias is in, as addmm
+    p, idx, w, s = KD.route_fwd(logits[:, :E], moe.biases, k, _forced(moe, T))
+    counts, offsets, slot, row_token, _ = KM.plan(idx, E)
+    max_vio = KD.bias_update(counts, moe.biases, moe.bias_update_rate)  # after this forward's router, on its stream
+    object.__setattr__(moe, "max_vio", max_vio.reshape(()))
+    object.__setattr__(moe, "_routed", (idx, counts))  # this forward's selection and counts, device tensors (tests and metrics; nothing here reads them back)
+    xs = KM.gather_rows(h, row_token)
+    if ops_moe.SEGMENTED:  # every product once over all routed experts, the segment table read on the device (ops_moe.experts_forward)
+        st = ops_moe.expert_stacks(moe, arena, moe.routed_experts, "lin_gate", "lin1")  # [u | g] = [lin_gate | lin1]: a = lin_gate(x) * silu(lin1(x))
+        gus, acts, y = ops_moe.experts_forward(st, xs, counts, offsets, T * k, F_)
+        segs = None
+    else:
+        y, gus, acts, segs = _experts_forward_loop(moe, arena, xs, counts, F_)
     sh_out, sh_saved = (None, None)
     if moe.num_shared > 0:
         sh_out, sh_saved = shared_forward(moe.shared_experts, h, keep)
     out = KD.combine_fwd(y, slot, w, sh_out, residual)
-    saved = (h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, wg8, sh_saved) if keep else None
+    saved = (h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, offsets, wg8, sh_saved) if keep else None
     return out, saved
 
 
-def moe_backward(moe, arena, saved, dout, wg):
-    """d(h) [T, d] of ``moe_forward`` (the residual's share is the caller's)."""
-    h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, wg8, sh_saved = saved
-    E, F_ = moe.num_routed, moe.routed_experts[0].hidden_dim
-    T = h.shape[0]
-    dy, dw = KM.combine_bwd(dout, row_token, slot, w, y)
+def _experts_backward_loop(moe, arena, xs, gus, acts, segs, dy, F_, wg):
+    """The per-expert path's d(xs): the forward's segment lengths again, the weight gradients recorded in ``wg``."""
     dxs = torch.empty_like(xs)
     for e, (off, n) in enumerate(segs):
         ex = moe.routed_experts[e]
@@ -192,6 +201,20 @@ def moe_backward(moe, arena, saved, dout, wg):
         ops._wgrad(arena, ex.lin2.weight, None, dy_e, a, wg)
         K.dgrad(dgu, arena.fused(ex.lin_gate.weight, ex.lin1.weight), out=dxs[off : off + n])
         ops._wgrad(arena, ex.lin_gate.weight, ex.lin1.weight, dgu, xs[off : off + n], wg)
+    return dxs
+
+
+def moe_backward(moe, arena, saved, dout, wg):
+    """d(h) [T, d] of ``moe_forward`` (the residual's share is the caller's)."""
+    h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, offsets, wg8, sh_saved = saved
+    E, F_ = moe.num_routed, moe.routed_experts[0].hidden_dim
+    T = h.shape[0]
+    dy, dw = KM.combine_bwd(dout, row_token, slot, w, y)
+    if segs is None:  # the forward ran segmented: gus / acts are the whole sorted buffers
+        st = ops_moe.expert_stacks(moe, arena, moe.routed_experts, "lin_gate", "lin1")
+        dxs = ops_moe.experts_backward(st, arena, xs, gus, acts, dy, counts, offsets, T * moe.top_k, F_)
+    else:
+        dxs = _experts_backward_loop(moe, arena, xs, gus, acts, segs, dy, F_, wg)
     dh = KM.combine_fwd(dxs, slot)  # the gather's backward
     # the gate: dlogits on the padded pitch (pad columns zero), dgrad on the padded weight, the weight gradient through an fp32 scratch
     Ep = wg8.shape[0]

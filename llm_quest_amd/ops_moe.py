@@ -1,11 +1,20 @@
 """Autograd layer of the Qwen3 mixture-of-experts path: the layer (``Qwen3MoE``) and the block (``MoETransformerBlock``) as ONE node each.
 
-The matrix products run on the existing GEMM launchers, one call per product for every expert that received tokens, on that expert's row
-segment of the expert-sorted buffers; everything else -- router, token-to-expert plan, row dispatch, weighted combine, their backwards -- is
-``csrc/moe.hip`` (launchers ``kernels_moe.py``).  The host reads the ``E`` counts once per layer and forward (the per-expert calls need the
-segment lengths); the backward reuses the numbers.  Nothing else in the layer synchronises.  A device-side segmented GEMM removes that read and
-the per-expert launches; it is the follow-up.
+The experts' matrix products run as segmented GEMMs (``K.gemm_segmented`` / ``K.gemm_segmented_wgrad``, csrc/gemm_segmented.hip): gate-up (+ SwiGLU), ``lin2``,
+the two dgrads and the two weight gradients are ONE launch each over all experts, on the expert-sorted buffers, with the segment table (the plan's
+``counts`` / ``offsets``) read on the device.  Forward and backward contain no device-to-host read and their launch count does not depend on the
+number of experts.  The experts' weights and gradients reach the kernels as stacks over the block's ``ParamArena`` (``expert_stacks``: one constant
+stride per expert); the weight gradients are written -- or accumulated, by ``arena.grad_target`` over the experts' parameter range -- in place, and an
+expert without a token ends with an exactly zero gradient.  Everything else -- router, token-to-expert plan, row dispatch, weighted combine, their
+backwards -- is ``csrc/moe.hip`` (launchers ``kernels_moe.py``).
+
+``MI355_MOE_SEGMENTED=0`` (``SEGMENTED``, read once) keeps the earlier per-expert path for same-box A/B runs and as the tests' comparison: the host
+reads the ``E`` counts once per forward, then runs two or three launches per expert that received tokens; its weight gradients go through the
+caller's grouped launches.  Per segment both paths compute the same sums (the segmented kernels are bit-identical to the per-expert calls on the
+128x128 tile).
 """
+
+import os
 
 import torch
 
@@ -15,6 +24,67 @@ from . import kernels_moe as KM
 from . import ops
 
 BF16, F32 = torch.bfloat16, torch.float32
+SEGMENTED = os.environ.get("MI355_MOE_SEGMENTED", "1") != "0"  # 0: one launch per expert and product, behind a host read of the counts (A/B measurements, the tests' comparison)
+
+
+# ----------------------------------------------------------------------------------------------- the experts as stacks
+class ExpertStacks:
+    """The experts' weights and gradients as 3-D stacks [E, rows, cols] over the arena (``K.expert_stack``): ``wgu`` [E, 2F, d] the fused gate-up pair,
+    ``w2`` [E, d, F], ``ggu`` / ``g2`` the same views of the gradient arena; ``first`` / ``last`` = the parameter range ``arena.grad_target`` covers."""
+
+    __slots__ = ("ptrs", "wgu", "w2", "ggu", "g2", "first", "last", "params")
+
+
+def expert_stacks(owner, arena, experts, up, gate):
+    """``owner``'s stacks, rebuilt when the arena moved.  ``up`` / ``gate`` name the two halves of the fused pair in the arena's order.  Raises unless every
+    expert's three parameters are consecutive in the arena and the experts follow each other at one stride."""
+    st = getattr(owner, "_expert_stacks", None)
+    if st is not None and st.ptrs is arena._ptrs:
+        return st
+    pairs = [(getattr(ex, up).weight, getattr(ex, gate).weight) for ex in experts]
+    st = ExpertStacks()
+    st.wgu = K.expert_stack([arena.fused(a, b) for a, b in pairs])
+    st.w2 = K.expert_stack([ex.lin2.weight.detach() for ex in experts])
+    st.first, st.last = pairs[0][0], experts[-1].lin2.weight
+    i, j = arena.index(st.first), arena.index(st.last)
+    if j - i + 1 != 3 * len(experts) or arena.data.storage_offset() != 0 or arena.grad.storage_offset() != 0:
+        raise RuntimeError("segmented MoE: the experts' parameters are not one consecutive range of the arena")
+    st.params = arena.params[i : j + 1]
+    st.ggu = arena.grad.as_strided(st.wgu.size(), st.wgu.stride(), st.wgu.storage_offset())
+    st.g2 = arena.grad.as_strided(st.w2.size(), st.w2.stride(), st.w2.storage_offset())
+    st.ptrs = arena._ptrs
+    object.__setattr__(owner, "_expert_stacks", st)
+    return st
+
+
+def experts_forward(st, xs, counts, offsets, max_rows, F_):
+    """(gu [R, 2F], a [R, F], y [R, d]) of all experts on the sorted rows ``xs``: two launches (three when F % 32 != 0 keeps the unfused SwiGLU kernel, which
+    then runs once over the whole sorted buffer; padding rows hold no defined value and are never read through slot / row_token)."""
+    if ops.FUSE_SWIGLU_FWD and F_ % 32 == 0:
+        gu, a = K.gemm_segmented(L.GEMM_NT, xs, st.wgu, counts, offsets, max_rows, epilogue="swiglu_fwd")
+    else:
+        gu = K.gemm_segmented(L.GEMM_NT, xs, st.wgu, counts, offsets, max_rows)
+        a = K.swiglu_fwd(gu, F_)
+    y = K.gemm_segmented(L.GEMM_NT, a, st.w2, counts, offsets, max_rows)
+    return gu, a, y
+
+
+def experts_backward(st, arena, xs, gu, a, dy, counts, offsets, max_rows, F_):
+    """d(xs) [R, d]; the experts' weight gradients go straight into the arena: two dgrad launches (+ the unfused SwiGLU backward when switched off) and two
+    weight-gradient launches over all experts.  An expert without a token ends with an exactly zero (or, accumulating, unchanged) attached gradient."""
+    if ops.FUSE_SWIGLU_BWD:
+        dgu = K.gemm_segmented(L.GEMM_NN, dy, st.w2, counts, offsets, max_rows, epilogue="swiglu_bwd", second=gu)
+    else:
+        dgu = K.swiglu_bwd(gu, K.gemm_segmented(L.GEMM_NN, dy, st.w2, counts, offsets, max_rows), F_)
+    dxs = K.gemm_segmented(L.GEMM_NN, dgu, st.wgu, counts, offsets, max_rows)
+    need = [p.requires_grad for p in st.params]
+    if all(need):
+        _, acc = arena.grad_target(st.first, st.last)  # attaches every expert's .grad, resolves mixed fresh / stale states
+        K.gemm_segmented_wgrad(dy, a, counts, offsets, st.g2, accumulate=acc)
+        K.gemm_segmented_wgrad(dgu, xs, counts, offsets, st.ggu, accumulate=acc)
+    elif any(need):
+        raise NotImplementedError("segmented MoE: the experts' weights must all be trainable or all frozen (MI355_MOE_SEGMENTED=0 runs the per-expert path)")
+    return dxs
 
 
 # ----------------------------------------------------------------------------------------------- the layer
@@ -36,17 +106,10 @@ def _gate_input(moe, h, gate_probas):
     return K.cast(gp.contiguous(), BF16), True
 
 
-def moe_forward(moe, arena, h, residual, gate_probas, keep):
-    """h bf16 [T, d] contiguous -> (residual + moe(h) [T, d], load loss fp32 [1] or None, the probabilities routed by, saved or None)."""
-    E, k, F_ = moe.num_experts, moe.top_k, moe.experts[0].hidden_dim
-    T, d = h.shape
-    gate_in, replay = _gate_input(moe, h, gate_probas)
-    p, idx, w, s = KM.route_fwd(gate_in, k, replay)
-    psum = K.colsum(p) if moe.training else None
-    counts, _, slot, row_token, loss = KM.plan(idx, E, psum, moe.load_coeff)
-    n_rows = counts.tolist()  # the layer's ONE device-to-host read: the per-expert launches need the segment lengths
+def _experts_forward_loop(moe, arena, xs, counts, F_):
+    """The per-expert path (``SEGMENTED`` off): the host reads the counts, then two or three launches per expert that received tokens."""
+    n_rows = counts.tolist()  # the device-to-host read the segmented path does without: the per-expert launches need the segment lengths
     align = KM.row_align()
-    xs = KM.gather_rows(h, row_token)
     y = torch.empty_like(xs)  # rows no expert writes (padding) are never read: the combine kernels go through slot / row_token
     fused = ops.FUSE_SWIGLU_FWD and F_ % 32 == 0
     segs, gus, acts, off = [], [], [], 0
@@ -67,17 +130,31 @@ def moe_forward(moe, arena, h, residual, gate_probas, keep):
         gus.append(gu)
         acts.append(a)
         off += (n + align - 1) // align * align
+    return y, gus, acts, segs
+
+
+def moe_forward(moe, arena, h, residual, gate_probas, keep):
+    """h bf16 [T, d] contiguous -> (residual + moe(h) [T, d], load loss fp32 [1] or None, the probabilities routed by, saved or None)."""
+    E, k, F_ = moe.num_experts, moe.top_k, moe.experts[0].hidden_dim
+    T, d = h.shape
+    gate_in, replay = _gate_input(moe, h, gate_probas)
+    p, idx, w, s = KM.route_fwd(gate_in, k, replay)
+    psum = K.colsum(p) if moe.training else None
+    counts, offsets, slot, row_token, loss = KM.plan(idx, E, psum, moe.load_coeff)
+    xs = KM.gather_rows(h, row_token)
+    if SEGMENTED:  # every product once over all experts, the segment table read on the device: no host read, no per-expert launch
+        st = expert_stacks(moe, arena, moe.experts, "lin1", "lin_gate")
+        gus, acts, y = experts_forward(st, xs, counts, offsets, T * k, F_)
+        segs = None
+    else:
+        y, gus, acts, segs = _experts_forward_loop(moe, arena, xs, counts, F_)
     out = KM.combine_fwd(y, slot, w, residual)
-    saved = (h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, replay) if keep else None
+    saved = (h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, offsets, replay) if keep else None
     return out, loss, p, saved
 
 
-def moe_backward(moe, arena, saved, dout, g_loss, wg):
-    """d(h) [T, d] of ``moe_forward`` (the residual's share is the caller's).  ``g_loss``: dL/d(load loss), fp32 [1] on the device, or None.
-    Weight gradients are recorded in ``wg`` for the caller's grouped launches."""
-    h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, replay = saved
-    F_ = moe.experts[0].hidden_dim
-    dy, dw = KM.combine_bwd(dout, row_token, slot, w, None if replay else y)
+def _experts_backward_loop(moe, arena, xs, gus, acts, segs, dy, F_, wg):
+    """The per-expert path's d(xs): the forward's segment lengths again, the weight gradients recorded in ``wg``."""
     dxs = torch.empty_like(xs)  # as y: only the rows in use are read back
     for e, (off, n) in enumerate(segs):
         ex = moe.experts[e]
@@ -96,6 +173,20 @@ def moe_backward(moe, arena, saved, dout, g_loss, wg):
         ops._wgrad(arena, ex.lin2.weight, None, dy_e, a, wg)
         K.dgrad(dgu, arena.fused(ex.lin1.weight, ex.lin_gate.weight), out=dxs[off : off + n])
         ops._wgrad(arena, ex.lin1.weight, ex.lin_gate.weight, dgu, xs[off : off + n], wg)
+    return dxs
+
+
+def moe_backward(moe, arena, saved, dout, g_loss, wg):
+    """d(h) [T, d] of ``moe_forward`` (the residual's share is the caller's).  ``g_loss``: dL/d(load loss), fp32 [1] on the device, or None.
+    The gate's weight gradient (and, on the per-expert path, the experts') is recorded in ``wg`` for the caller's grouped launches."""
+    h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, offsets, replay = saved
+    F_ = moe.experts[0].hidden_dim
+    dy, dw = KM.combine_bwd(dout, row_token, slot, w, None if replay else y)
+    if segs is None:  # the forward ran segmented: gus / acts are the whole sorted buffers
+        st = expert_stacks(moe, arena, moe.experts, "lin1", "lin_gate")
+        dxs = experts_backward(st, arena, xs, gus, acts, dy, counts, offsets, h.shape[0] * moe.top_k, F_)
+    else:
+        dxs = _experts_backward_loop(moe, arena, xs, gus, acts, segs, dy, F_, wg)
     dh = KM.combine_fwd(dxs, slot)  # the gather's backward: dh[t] = sum_j dxs[slot[t, j]]
     if not replay:  # a replayed routing is a constant: the gate is not evaluated and gets no gradient
         dlogits = KM.route_bwd(dw, w, s, idx, p, counts, g_loss, moe.load_coeff)

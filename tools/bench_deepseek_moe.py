@@ -5,7 +5,8 @@
 One DeepSeekMoE layer of ``DEEPSEEK_SMALL_CONFIG`` (emb 768, 7 routed + 1 shared expert of hidden 768, top_k 3), forward + backward on
 ``--tokens`` tokens, and its split as ``bench_moe.py`` splits: router and bias update (gate GEMM, route forward / backward, the update), plan,
 rows (dispatch, combine and their backwards), shared experts, routed expert GEMMs (per-expert launches on the layer's own counts, the host read
-included).  The dense ``FFN`` of the same config (hidden 3072) on the same tokens in the same run.  Then the training step of
+included, and the six segmented launches).  The layer and the model steps run with ``ops_moe.SEGMENTED`` on and off in this one process: both medians
+and their ratio are in the output.  The dense ``FFN`` of the same config (hidden 3072) on the same tokens in the same run.  Then the training step of
 ``DEEPSEEK_SMALL_CONFIG`` as written (3 dense + 9 MoE blocks, mtp_depth 2) beside the all-dense one ``bench_deepseek.py`` measures.
 
 Times are device events around whole calls, medians after warm-up, no profiler attached; one JSON line per measurement on stdout, all of them
@@ -47,7 +48,7 @@ def measure_layer(cfg, T, steps, warmup):
     from llm_quest_amd import kernels as K
     from llm_quest_amd import kernels_dsmoe as KD
     from llm_quest_amd import kernels_moe as KM
-    from llm_quest_amd import ops, ops_dsmoe
+    from llm_quest_amd import ops, ops_dsmoe, ops_moe
     from llm_quest_amd.moe.deepseek_moe import DeepSeekMoE
 
     torch.manual_seed(0)
@@ -64,14 +65,23 @@ def measure_layer(cfg, T, steps, warmup):
         x.grad = None
         moe(x).backward(dy)
 
-    whole()
+    # switch on (segmented GEMMs over all routed experts, no host read) and off (per-expert launches behind the read of the counts), same process, same
+    # tensors; the shipped default last
+    default, by_switch = ops_moe.SEGMENTED, {}
+    for on in (not default, default):
+        ops_moe.SEGMENTED = on
+        whole()
+        by_switch[on] = time_calls(whole, steps, warmup)
     arena = ops_dsmoe.ensure_arena(moe)
     idx, counts = moe._routed
-    out = [dict(kind="layer", name="DeepSeekMoE forward + backward", tokens=T, counts=counts.tolist(), **time_calls(whole, steps, warmup))]
+    out = [dict(kind="layer", name="DeepSeekMoE forward + backward", tokens=T, counts=counts.tolist(), default_path="segmented" if default else "per-expert",
+                segmented_ms_median=by_switch[True]["ms_median"], segmented_ms_min=by_switch[True]["ms_min"], segmented_ms_max=by_switch[True]["ms_max"],
+                per_expert_ms_median=by_switch[False]["ms_median"], per_expert_ms_min=by_switch[False]["ms_min"], per_expert_ms_max=by_switch[False]["ms_max"],
+                per_expert_over_segmented=by_switch[False]["ms_median"] / by_switch[True]["ms_median"], **by_switch[default])]
     wg8, bg8 = ops_dsmoe._gate_operands(moe)
     logits = K.gemm(L.GEMM_NT, h, wg8, bias=bg8)
     p, idx, w, s = KD.route_fwd(logits[:, :E], moe.biases, k)
-    counts, _, slot, row_token, _ = KM.plan(idx, E)
+    counts, offsets, slot, row_token, _ = KM.plan(idx, E)
     xs = KM.gather_rows(h, row_token)
     y = torch.randn(xs.shape, generator=g).to(BF16).cuda()
     dw = torch.randn(T, k, generator=g).cuda()
@@ -123,7 +133,14 @@ def measure_layer(cfg, T, steps, warmup):
             off += (n + align - 1) // align * align
         ops_dsmoe._flush(wg)
 
-    parts = [("router and bias update", router), ("plan", plan), ("rows", rows), ("routed expert GEMMs", experts)]
+    st = ops_moe.expert_stacks(moe, arena, moe.routed_experts, "lin_gate", "lin1")
+
+    def experts_segmented():
+        gu, a, _ = ops_moe.experts_forward(st, xs, counts, offsets, T * k, F_)
+        ops_moe.experts_backward(st, arena, xs, gu, a, y, counts, offsets, T * k, F_)
+
+    parts = [("router and bias update", router), ("plan", plan), ("rows", rows), ("routed expert GEMMs, per-expert launches (host read included)", experts),
+             ("routed expert GEMMs, segmented (one launch per product, no host read)", experts_segmented)]
     if moe.num_shared > 0:
         parts.insert(3, ("shared experts", shared))
     for name, fn in parts:
@@ -171,8 +188,17 @@ def measure_step(cfg, label, batch, seq, steps, warmup):
         loss.backward()
         return loss.detach()
 
+    from llm_quest_amd import ops_moe
+
     loss = float(step())
-    r = time_calls(step, steps, warmup)
+    default, by_switch = ops_moe.SEGMENTED, {}
+    for on in (not default, default):  # (an all-dense model has no MoE layer: its two times show the run-to-run spread of this measurement)
+        ops_moe.SEGMENTED = on
+        step()
+        by_switch[on] = time_calls(step, steps, warmup)
+    r = dict(by_switch[default])
+    r.update(segmented_ms_median=by_switch[True]["ms_median"], per_expert_ms_median=by_switch[False]["ms_median"],
+             per_expert_over_segmented=by_switch[False]["ms_median"] / by_switch[True]["ms_median"])
     r.update(kind="step", model=label, batch=batch, seq=seq, tokens=batch * seq, loss=loss, parameters=sum(p.numel() for p in m.parameters()),
              peak_mem_gb=torch.cuda.max_memory_allocated() / 2**30)
     r["tokens_per_s"] = batch * seq / (r["ms_median"] * 1e-3)

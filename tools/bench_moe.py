@@ -4,14 +4,15 @@
 
 Subject: one ``Qwen3MoE`` layer, forward + backward, at the ``temp_moe`` shape (d = 896, F = 3584, E = 16, k = 4) on T = 4096 tokens, routed by
 a trained-like gate (gate weights scaled so that the probabilities are peaked; random tokens).  On the same box, in the same process:
-  * the whole layer (``ops_moe.MoEFn``), device events around forward + backward;
-  * its split: the row kernels of csrc/moe.hip alone (route, column sums, plan, gather, combine, their backwards), the expert GEMMs alone (the
-    per-expert loop of the layer on prepared segments, forward + backward with the weight gradients), the gate's three GEMMs, and the host's
+  * the whole layer (``ops_moe.MoEFn``), device events around forward + backward, with ``ops_moe.SEGMENTED`` on (segmented GEMMs: one launch per product
+    over all experts, no host read) and off (per-expert launches behind the read of the counts): both medians and their ratio, from this one run;
+  * its split: the row kernels of csrc/moe.hip alone (route, column sums, plan, gather, combine, their backwards), the expert GEMMs alone (forward + backward
+    with the weight gradients on prepared segments: the per-expert loop, and the six segmented launches), the gate's three GEMMs, and the host's
     wait on the ``E`` counts (host clock around the one device-to-host read, queue drained before the router is enqueued);
   * the dense SwiGLU FFN of the same activated width (hidden = k * F) through the existing kernels, forward + backward;
-  * one ``30B-A3B``-shaped layer (d = 2048, F = 768, E = 128, k = 8): what 128 experts' launches cost.
-Medians after warm-up, no profiler attached; one JSON line per measurement on stdout, all of them in ``--out``.  No threshold: these are the
-first numbers of this path.  Needs the GPU.
+  * one ``30B-A3B``-shaped layer (d = 2048, F = 768, E = 128, k = 8), both paths: what 128 experts' launches cost.
+Medians after warm-up, no profiler attached; one JSON line per measurement on stdout, all of them in ``--out``.  No threshold: the comparison is the
+other path in the same run.  Needs the GPU.
 """
 
 import argparse
@@ -76,8 +77,14 @@ def measure_layer(name, d, F_, E, k, T, steps, warmup, split):
         torch.autograd.backward([out, moe.moe_loss], [dy, one])
         return xg.grad
 
-    whole()
-    r = time_calls(whole, steps, warmup)
+    # the layer with the switch on (segmented GEMMs: no host read, one launch per product) and off (per-expert launches behind the read of the counts),
+    # same process, same tensors, the shipped default last so that everything below runs on it
+    default, by_switch = ops_moe.SEGMENTED, {}
+    for on in (not default, default):
+        ops_moe.SEGMENTED = on
+        whole()
+        by_switch[on] = time_calls(whole, steps, warmup)
+    r = by_switch[default]
     arena = ops.arena_for(moe)
     h = x[0]
     logits = K.gemm(L.GEMM_NT, h, moe.gate.weight)
@@ -87,8 +94,13 @@ def measure_layer(name, d, F_, E, k, T, steps, warmup, split):
     hit = sum(1 for n in n_rows if n)
     res = dict(kind="layer", name=name, d=d, F=F_, E=E, k=k, T=T, fwd_bwd_ms=r["ms_median"], fwd_bwd_ms_min=r["ms_min"], fwd_bwd_ms_max=r["ms_max"], steps=steps,
                experts_hit=hit, rows_min=min(n_rows), rows_max=max(n_rows),
-               launches=dict(expert_gemms_fwd=2 * hit, expert_gemms_bwd=2 * hit, weight_gradient_problems=2 * hit + 1, grouped_weight_gradient_launches=(2 * hit + 1 + 7) // 8,
-                             row_kernels=10, gate_gemms=3))
+               default_path="segmented" if default else "per-expert",
+               segmented_fwd_bwd_ms=by_switch[True]["ms_median"], segmented_fwd_bwd_ms_min=by_switch[True]["ms_min"], segmented_fwd_bwd_ms_max=by_switch[True]["ms_max"],
+               per_expert_fwd_bwd_ms=by_switch[False]["ms_median"], per_expert_fwd_bwd_ms_min=by_switch[False]["ms_min"], per_expert_fwd_bwd_ms_max=by_switch[False]["ms_max"],
+               per_expert_over_segmented=by_switch[False]["ms_median"] / by_switch[True]["ms_median"],
+               launches=dict(segmented=dict(expert_gemms_fwd=2, expert_gemms_bwd=2, weight_gradient_launches=2, gate_weight_gradient_launches=1, row_kernels=10, gate_gemms=3),
+                             per_expert=dict(expert_gemms_fwd=2 * hit, expert_gemms_bwd=2 * hit, weight_gradient_problems=2 * hit + 1,
+                                             grouped_weight_gradient_launches=(2 * hit + 1 + 7) // 8, row_kernels=10, gate_gemms=3)))
     if not split:
         return [res]
     out = [res]
@@ -135,7 +147,16 @@ def measure_layer(name, d, F_, E, k, T, steps, warmup, split):
             ops._wgrad(arena, ex.lin1.weight, ex.lin_gate.weight, dgu, xs[o : o + n], wg)
         ops._flush_wgrads(wg)
 
-    out.append(dict(kind="split", name=name, part="expert GEMMs (gate-up + SwiGLU, lin2, their dgrads, grouped weight gradients)", **time_calls(experts, steps, warmup)))
+    out.append(dict(kind="split", name=name, part="expert GEMMs, per-expert launches (gate-up + SwiGLU, lin2, their dgrads, grouped weight gradients)",
+                    **time_calls(experts, steps, warmup)))
+    st = ops_moe.expert_stacks(moe, arena, moe.experts, "lin1", "lin_gate")
+
+    def experts_segmented():
+        gu, a, _ = ops_moe.experts_forward(st, xs, counts, offsets, T * k, F_)
+        ops_moe.experts_backward(st, arena, xs, gu, a, y, counts, offsets, T * k, F_)
+
+    out.append(dict(kind="split", name=name, part="expert GEMMs, segmented (the same six products, one launch each over all experts, no host read)",
+                    **time_calls(experts_segmented, steps, warmup)))
     dlogits = torch.randn(logits.shape, generator=torch.Generator().manual_seed(6)).to(BF16).cuda()
     dh = torch.zeros_like(h)
 
