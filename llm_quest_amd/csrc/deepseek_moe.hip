@@ -4,30 +4,18 @@
 //             index), weights from the UNBIASED probabilities, renormalised; or, with a forced selection, the weights of the given experts
 //   update    biases += rate * sign(mean(counts) - counts) and max_vio = (max(counts) - mean) / mean, from the counts mi355_moe_plan wrote
 //   silu      the shared experts' bias + SiLU between their two products, forward and backward, over [T, n * hidden] rows
-//   combine   out[t] = residual[t] + shared[t] + sum_j w[t, j] * Y[slot[t, j]]   (fp32, one rounding)
+//   combine   out[t] = residual[t] + (shared[t] + sum_j w[t, j] * Y[slot[t, j]])   (fp32, one rounding): the entry point only; kernel and launcher are moe.hip's
 //   colsum    column sums of bf16 rows as per-row-part partials in a fixed order (the bias gradients)
 //
-// The plan, the row dispatch, the combine's backward and the router's backward are moe.hip's (mi355_moe_route_bwd takes any E in 1..128).
+// The plan, the row dispatch, the combine's backward and the router's backward are moe.hip's (mi355_moe_route_bwd takes any E in 1..128); the limits, the
+// host checks and the two ends of the router kernel (the token's softmax, the write-out of s / idx / w) are shared with it through moe_common.h.
 // No atomics, one writer per element, fixed summation orders.  Rounding points are the reference's bf16 tensors:
 //   p = bf16(softmax), key = p + biases in the promoted dtype, s = bf16(sum_j v_j), w_j = bf16(v_j / s)     (deepseek_moe.py:180-186)
 //   pre = bf16(bf16(x W1) + b1), act = bf16(silu(pre))                                                        (deepseek_moe.py:82-88, 125-126)
-#include <initializer_list>
-
-#include "rows_bf16.h"
+#include "moe_common.h"
 
 namespace {
 
-constexpr int DSM_MAX_E = 128;  // two experts per lane
-constexpr int DSM_MAX_K = 8;
-
-__device__ __forceinline__ unsigned wave_umax(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned u = (unsigned)__shfl_xor((int)v, o, 64);
-        v = u > v ? u : v;
-    }
-    return v;
-}
 __device__ __forceinline__ unsigned wave_umin(unsigned v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -59,26 +47,20 @@ __global__ __launch_bounds__(256) void dsmoe_route_fwd_kernel(int64_t T, int E, 
             if (lane + 64 * h < E) bv[h] = BIAS_F32 ? ((const float*)bias)[lane + 64 * h] : bf2f(((const bf16_t*)bias)[lane + 64 * h]);
     }
     for (int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); t < T; t += waves) {
-        const bf16_t* row = logits + t * ldl;
-        float x[2], e[2], pf[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) x[h] = lane + 64 * h < E ? bf2f(row[lane + 64 * h]) : -INFINITY;
-        const float m = wave_max(fmaxf(x[0], x[1]));
-#pragma unroll
-        for (int h = 0; h < 2; ++h) e[h] = lane + 64 * h < E ? expf(x[h] - m) : 0.f;
-        const float den = wave_sum(e[0] + e[1]);
+        bf16_t pb[2];
+        float pf[2];
+        route_softmax(logits + t * ldl, E, lane, pb);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const bf16_t pb = f2bf(e[h] / den);
-            pf[h] = bf2f(pb);
-            if (lane + 64 * h < E) p[t * ldp + lane + 64 * h] = pb;
+            pf[h] = bf2f(pb[h]);
+            if (lane + 64 * h < E) p[t * ldp + lane + 64 * h] = pb[h];
         }
-        float v[DSM_MAX_K];
-        int ex[DSM_MAX_K];
+        float v[MOE_MAX_K];
+        int ex[MOE_MAX_K];
         float sum = 0.f;
         if (FORCED) {
 #pragma unroll
-            for (int j = 0; j < DSM_MAX_K; ++j)
+            for (int j = 0; j < MOE_MAX_K; ++j)
                 if (j < k) {
                     const int f = forced[t * k + j];
                     const bool ok = f >= 0 && f < E;  // not an expert: weight 0, and mi355_moe_plan gives the assignment no row
@@ -95,7 +77,7 @@ __global__ __launch_bounds__(256) void dsmoe_route_fwd_kernel(int64_t T, int E, 
                 key[h] = lane + 64 * h < E ? order_f32(kf) : 0u;
             }
 #pragma unroll
-            for (int j = 0; j < DSM_MAX_K; ++j)
+            for (int j = 0; j < MOE_MAX_K; ++j)
                 if (j < k) {
                     const unsigned best = wave_umax(key[0] > key[1] ? key[0] : key[1]);
                     const unsigned mine = (key[0] != 0u && key[0] == best) ? (unsigned)lane : ((key[1] != 0u && key[1] == best) ? (unsigned)(lane + 64) : 255u);
@@ -108,16 +90,7 @@ __global__ __launch_bounds__(256) void dsmoe_route_fwd_kernel(int64_t T, int E, 
                     if (sel == lane + 64) key[1] = 0u;
                 }
         }
-        const float sr = rbf(sum);
-        if (lane == 0) {
-            s[t] = sr;
-#pragma unroll
-            for (int j = 0; j < DSM_MAX_K; ++j)
-                if (j < k) {
-                    idx[t * k + j] = ex[j];
-                    w[t * k + j] = f2bf(v[j] / sr);
-                }
-        }
+        route_write(t, k, lane, ex, v, sum, idx, w, s);
     }
 }
 
@@ -125,7 +98,7 @@ __global__ __launch_bounds__(256) void dsmoe_route_fwd_kernel(int64_t T, int E, 
 // ONE workgroup, thread e owns expert e: one writer per bias, the two reductions in LDS in a fixed order.
 template <bool BIAS_F32>
 __global__ __launch_bounds__(128) void dsmoe_bias_update_kernel(int E, const int* __restrict__ counts, void* __restrict__ biases, float rate, float* __restrict__ max_vio) {
-    __shared__ int cs[DSM_MAX_E];
+    __shared__ int cs[MOE_MAX_E];
     __shared__ float stat[2];
     const int e = threadIdx.x;
     const int c = e < E ? counts[e] : 0;
@@ -196,39 +169,6 @@ __global__ __launch_bounds__(256) void dsmoe_bias_silu_bwd_kernel(int64_t T, int
     }
 }
 
-// ------------------------------------------------------------------------------------------------ combine with the shared experts' output
-__global__ __launch_bounds__(256) void dsmoe_combine_fwd_kernel(int64_t T, int64_t R, int k, int c8, const int* __restrict__ slot, const bf16_t* __restrict__ w,
-                                                                const bf16_t* __restrict__ y, int64_t ldy, const bf16_t* __restrict__ sh, int64_t lds,
-                                                                const bf16_t* __restrict__ res, int64_t ldr, bf16_t* __restrict__ out, int64_t ldo) {
-    const int64_t n = T * c8, stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        const int64_t t = i / c8;
-        const int c = (int)(i - t * c8);
-        float acc[8], f[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-        for (int j = 0; j < k; ++j) {
-            const int r = slot[t * k + j];
-            if (r < 0 || r >= R) continue;
-            const float wj = bf2f(w[t * k + j]);
-            unpack8(*(const u32x4*)(y + (int64_t)r * ldy + c * 8), f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] += wj * f[e];
-        }
-        if (sh != nullptr) {
-            unpack8(*(const u32x4*)(sh + t * lds + c * 8), f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] = f[e] + acc[e];
-        }
-        if (res != nullptr) {
-            unpack8(*(const u32x4*)(res + t * ldr + c * 8), f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] = f[e] + acc[e];
-        }
-        *(u32x4*)(out + t * ldo + c * 8) = pack8(acc);
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ column sums in a fixed order (bias gradients)
 // mi355_colsum folds its row blocks with fp32 atomics, whose order is not fixed.  Here workgroup (x, y) owns 512 columns of row part y: the four waves take rows
 // r, r + 1, r + 2, r + 3, meet in LDS and write parts[y, column] -- one writer; mi355_reduce_rows_f32 folds the parts.
@@ -256,34 +196,14 @@ __global__ __launch_bounds__(256) void dsmoe_colsum_parts_kernel(int64_t T, int 
     }
 }
 
-bool aligned16(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if ((uintptr_t)p & 15) return false;
-    return true;
-}
-
-inline int capped_grid(int64_t blocks) { return (int)(blocks < 1 ? 1 : (blocks > 16384 ? 16384 : blocks)); }
-
-int check_rows(const char* who, int64_t T, int d, std::initializer_list<int64_t> lds) {
-    MI355_REQUIRE(T < (int64_t)1 << 31, "%s: row counts must stay below 2^31 (got %ld)", who, (long)T);
-    MI355_REQUIRE(d > 0 && (d & 7) == 0, "%s: the row width must be a positive multiple of 8 (got %d)", who, d);
-    for (int64_t ld : lds) MI355_REQUIRE(ld >= d && (ld & 7) == 0, "%s: a leading dimension must be a multiple of 8 and at least the row width %d (got %ld)", who, d, (long)ld);
-    return 0;
-}
-
 bool bias_dtype_ok(int dt) { return dt == MI355_DT_BF16 || dt == MI355_DT_F32; }
 
 }  // namespace
 
-#define ST(s) ((hipStream_t)(s))
-
 extern "C" int mi355_dsmoe_route_fwd(int64_t T, int E, int k, const void* logits, int64_t ldl, const void* biases, int bias_dtype, const int32_t* forced_idx,
                                      void* p, int64_t ldp, int32_t* idx, void* w, float* s, void* stream) {
     if (T <= 0) return 0;
-    MI355_REQUIRE(E >= 1 && E <= DSM_MAX_E, "mi355_dsmoe_route_fwd: the number of routed experts must be in 1..%d (got %d)", DSM_MAX_E, E);
-    MI355_REQUIRE(k >= 1 && k <= DSM_MAX_K && k <= E, "mi355_dsmoe_route_fwd: top_k must be in 1..%d and at most the routed experts = %d (got %d)", DSM_MAX_K, E, k);
-    MI355_REQUIRE(T < (int64_t)1 << 31 && T * k + 64 * (int64_t)E < (int64_t)1 << 31, "mi355_dsmoe_route_fwd: tokens * top_k + 64 * experts must stay below 2^31 (tokens = %ld)",
-                  (long)T);
+    if (check_route("mi355_dsmoe_route_fwd", T, E, k)) return 1;
     MI355_REQUIRE(logits && p && idx && w && s, "mi355_dsmoe_route_fwd: null pointer");
     MI355_REQUIRE(forced_idx || biases, "mi355_dsmoe_route_fwd: the selection needs the balancing biases unless it is forced");
     MI355_REQUIRE(forced_idx || bias_dtype_ok(bias_dtype), "mi355_dsmoe_route_fwd: the biases are bf16 or fp32 (got dtype code %d)", bias_dtype);
@@ -301,7 +221,7 @@ extern "C" int mi355_dsmoe_route_fwd(int64_t T, int E, int k, const void* logits
 }
 
 extern "C" int mi355_dsmoe_bias_update(int E, const int32_t* counts, void* biases, int bias_dtype, float rate, float* max_vio, void* stream) {
-    MI355_REQUIRE(E >= 1 && E <= DSM_MAX_E, "mi355_dsmoe_bias_update: the number of routed experts must be in 1..%d (got %d)", DSM_MAX_E, E);
+    MI355_REQUIRE(E >= 1 && E <= MOE_MAX_E, "mi355_dsmoe_bias_update: the number of routed experts must be in 1..%d (got %d)", MOE_MAX_E, E);
     MI355_REQUIRE(counts && biases, "mi355_dsmoe_bias_update: null pointer");
     MI355_REQUIRE(bias_dtype_ok(bias_dtype), "mi355_dsmoe_bias_update: the biases are bf16 or fp32 (got dtype code %d)", bias_dtype);
     if (bias_dtype == MI355_DT_F32)
@@ -333,20 +253,12 @@ extern "C" int mi355_dsmoe_bias_silu_bwd(int64_t T, int N, const void* pre, int6
     return 0;
 }
 
+// The combine kernel and its launcher are moe.hip's; this entry point adds the shared operand and insists on the weights.
 extern "C" int mi355_dsmoe_combine_fwd(int64_t T, int64_t R, int k, int d, const int32_t* slot, const void* w, const void* y, int64_t ldy, const void* shared, int64_t lds,
                                        const void* residual, int64_t ldr, void* out, int64_t ldo, void* stream) {
     if (T <= 0) return 0;
-    MI355_REQUIRE(k >= 1 && k <= DSM_MAX_K, "mi355_dsmoe_combine_fwd: top_k must be in 1..%d (got %d)", DSM_MAX_K, k);
-    if (check_rows("mi355_dsmoe_combine_fwd", T, d, {ldy, ldo})) return 1;
-    if (shared && check_rows("mi355_dsmoe_combine_fwd", T, d, {lds})) return 1;
-    if (residual && check_rows("mi355_dsmoe_combine_fwd", T, d, {ldr})) return 1;
-    MI355_REQUIRE(R > 0 && R < (int64_t)1 << 31, "mi355_dsmoe_combine_fwd: the sorted rows must be positive and below 2^31 (got %ld)", (long)R);
-    MI355_REQUIRE(slot && w && y && out, "mi355_dsmoe_combine_fwd: null pointer");
-    MI355_REQUIRE(aligned16({y, shared, residual, out}), "mi355_dsmoe_combine_fwd: y, shared, residual and out must be 16-byte aligned");
-    dsmoe_combine_fwd_kernel<<<capped_grid((T * (d >> 3) + 255) / 256), 256, 0, ST(stream)>>>(T, R, k, d >> 3, slot, (const bf16_t*)w, (const bf16_t*)y, ldy,
-                                                                                                 (const bf16_t*)shared, lds, (const bf16_t*)residual, ldr, (bf16_t*)out, ldo);
-    MI355_LAUNCH_CHECK("mi355_dsmoe_combine_fwd");
-    return 0;
+    MI355_REQUIRE(w, "mi355_dsmoe_combine_fwd: null pointer (the routed experts' weights)");
+    return moe_combine_fwd_launch("mi355_dsmoe_combine_fwd", T, R, k, d, slot, w, y, ldy, shared, lds, residual, ldr, out, ldo, stream);
 }
 
 extern "C" int mi355_dsmoe_colsum_parts(int64_t T, int N, const void* x, int64_t ldx, float* parts, int n_parts, void* stream) {

@@ -5,7 +5,8 @@
 //             slot[t, j] = the row of assignment (t, j) in the expert-sorted buffer, row_token[r] = its inverse (-1 on padding rows), and the
 //             load-balancing loss from the counts and the column sums of the probabilities
 //   gather    Xs[r] = x[row_token[r]]                                (padding rows zero)
-//   combine   out[t] = residual[t] + sum_j w[t, j] * Y[slot[t, j]]   (j ascending, fp32, one rounding) -- also the gather's backward with w = NULL
+//   combine   out[t] = residual[t] + (shared[t] + sum_j w[t, j] * Y[slot[t, j]])   (j ascending, fp32, one rounding) -- also the gather's backward with w = NULL;
+//             the ONE combine kernel and its launcher: mi355_dsmoe_combine_fwd (deepseek_moe.hip) supplies ``shared``, mi355_moe_combine_fwd passes none
 //   and the backwards of combine and route.
 //
 // The expert products themselves run as segmented GEMMs (gemm_segmented.hip: mi355_gemm_bf16_segmented / _segmented_tn), one launch per product over all experts, on the
@@ -15,25 +16,13 @@
 // chunks and experts, the scatter), every output element has exactly one writer, every sum a fixed order -- two runs give the same bits.
 // Rows move 16 bytes per lane; sums are fp32 and are rounded to bf16 exactly where the reference's bf16 tensors are:
 //   p = bf16(softmax), s = bf16(sum_j v_j), w_j = bf16(v_j / s)      (qwen3_moe.py:113-121)
-#include <initializer_list>
-
-#include "rows_bf16.h"
+// The limits, the host checks and the two ends of the router kernel that deepseek_moe.hip uses as well are moe_common.h.
+#include "moe_common.h"
 
 namespace {
 
 constexpr int MOE_ALIGN = 32;     // rows: every expert's segment starts at a multiple of this
-constexpr int MOE_MAX_E = 128;    // two probabilities per lane in the route kernels
-constexpr int MOE_MAX_K = 8;
 constexpr int PLAN_CHUNK = 2048;  // assignments per workgroup of the counting pass
-
-__device__ __forceinline__ unsigned wave_umax(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned u = (unsigned)__shfl_xor((int)v, o, 64);
-        v = u > v ? u : v;
-    }
-    return v;
-}
 
 // bf16 bits -> an unsigned short that orders like the value (negative values below positive ones)
 __device__ __forceinline__ unsigned order_bits(bf16_t b) { return (b & 0x8000u) ? (~(unsigned)b & 0xffffu) : ((unsigned)b | 0x8000u); }
@@ -54,16 +43,7 @@ __global__ __launch_bounds__(256) void moe_route_fwd_kernel(int64_t T, int E, in
 #pragma unroll
             for (int h = 0; h < 2; ++h) pb[h] = lane + 64 * h < E ? row[lane + 64 * h] : (bf16_t)0;
         } else {
-            float x[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) x[h] = lane + 64 * h < E ? bf2f(row[lane + 64 * h]) : -INFINITY;
-            const float m = wave_max(fmaxf(x[0], x[1]));
-            float e[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) e[h] = lane + 64 * h < E ? expf(x[h] - m) : 0.f;
-            const float den = wave_sum(e[0] + e[1]);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) pb[h] = f2bf(e[h] / den);
+            route_softmax(row, E, lane, pb);
         }
         if (p != nullptr) {
 #pragma unroll
@@ -87,16 +67,7 @@ __global__ __launch_bounds__(256) void moe_route_fwd_kernel(int64_t T, int E, in
                 if (key[1] == best) key[1] = 0u;
             }
         }
-        const float sr = rbf(sum);
-        if (lane == 0) {
-            s[t] = sr;
-#pragma unroll
-            for (int j = 0; j < MOE_MAX_K; ++j)
-                if (j < k) {
-                    idx[t * k + j] = ex[j];
-                    w[t * k + j] = f2bf(v[j] / sr);
-                }
-        }
+        route_write(t, k, lane, ex, v, sum, idx, w, s);
     }
 }
 
@@ -216,9 +187,10 @@ __global__ __launch_bounds__(256) void moe_gather_kernel(int64_t R, int64_t T, i
     }
 }
 
+// out[t] = res[t] + (sh[t] + sum_j w[t, j] * Y[slot[t, j]]); w (weights of 1), sh and res may each be null -- both combine entry points launch this kernel
 __global__ __launch_bounds__(256) void moe_combine_fwd_kernel(int64_t T, int64_t R, int k, int c8, const int* __restrict__ slot, const bf16_t* __restrict__ w,
-                                                              const bf16_t* __restrict__ y, int64_t ldy, const bf16_t* __restrict__ res, int64_t ldr,
-                                                              bf16_t* __restrict__ out, int64_t ldo) {
+                                                              const bf16_t* __restrict__ y, int64_t ldy, const bf16_t* __restrict__ sh, int64_t lds,
+                                                              const bf16_t* __restrict__ res, int64_t ldr, bf16_t* __restrict__ out, int64_t ldo) {
     const int64_t n = T * c8, stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
         const int64_t t = i / c8;
@@ -233,6 +205,11 @@ __global__ __launch_bounds__(256) void moe_combine_fwd_kernel(int64_t T, int64_t
             unpack8(*(const u32x4*)(y + (int64_t)r * ldy + c * 8), f);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] += wj * f[e];
+        }
+        if (sh != nullptr) {
+            unpack8(*(const u32x4*)(sh + t * lds + c * 8), f);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = f[e] + acc[e];
         }
         if (res != nullptr) {
             unpack8(*(const u32x4*)(res + t * ldr + c * 8), f);
@@ -282,34 +259,9 @@ __global__ __launch_bounds__(256) void moe_combine_bwd_kernel(int64_t T, int64_t
     }
 }
 
-bool aligned16(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if ((uintptr_t)p & 15) return false;
-    return true;
-}
-
-inline int capped_grid(int64_t blocks) { return (int)(blocks < 1 ? 1 : (blocks > 16384 ? 16384 : blocks)); }
-
 int64_t plan_chunks(int64_t T, int k) { return (T * k + PLAN_CHUNK - 1) / PLAN_CHUNK; }
 
-// 1 <= k <= 8, k <= E <= 128, T * k + 64 * E < 2^31
-int check_route(const char* who, int64_t T, int E, int k) {
-    MI355_REQUIRE(E >= 1 && E <= MOE_MAX_E, "%s: num_experts must be in 1..%d (got %d)", who, MOE_MAX_E, E);
-    MI355_REQUIRE(k >= 1 && k <= MOE_MAX_K && k <= E, "%s: top_k must be in 1..%d and at most num_experts = %d (got %d)", who, MOE_MAX_K, E, k);
-    MI355_REQUIRE(T < (int64_t)1 << 31 && T * k + 64 * (int64_t)E < (int64_t)1 << 31, "%s: tokens * top_k + 64 * num_experts must stay below 2^31 (tokens = %ld)", who,
-                  (long)T);
-    return 0;
-}
-
-int check_rows(const char* who, int d, std::initializer_list<int64_t> lds) {
-    MI355_REQUIRE(d > 0 && (d & 7) == 0, "%s: the row width must be a positive multiple of 8 (got %d)", who, d);
-    for (int64_t ld : lds) MI355_REQUIRE(ld >= d && (ld & 7) == 0, "%s: a leading dimension must be a multiple of 8 and at least the row width %d (got %ld)", who, d, (long)ld);
-    return 0;
-}
-
 }  // namespace
-
-#define ST(s) ((hipStream_t)(s))
 
 extern "C" int mi355_moe_row_align(void) { return MOE_ALIGN; }
 
@@ -376,8 +328,7 @@ extern "C" int mi355_moe_plan(int64_t T, int E, int k, const int32_t* idx, int32
 
 extern "C" int mi355_moe_gather_rows(int64_t R, int64_t T, int d, const int32_t* row_token, const void* x, int64_t ldx, void* xs, int64_t ldxs, void* stream) {
     if (R <= 0 || T <= 0) return 0;
-    if (check_rows("mi355_moe_gather_rows", d, {ldx, ldxs})) return 1;
-    MI355_REQUIRE(R < (int64_t)1 << 31 && T < (int64_t)1 << 31, "mi355_moe_gather_rows: row counts must stay below 2^31");
+    if (check_rows("mi355_moe_gather_rows", T, d, {ldx}) || check_rows("mi355_moe_gather_rows", R, d, {ldxs})) return 1;
     MI355_REQUIRE(row_token && x && xs, "mi355_moe_gather_rows: null pointer");
     MI355_REQUIRE(aligned16({x, xs}), "mi355_moe_gather_rows: x and xs must be 16-byte aligned");
     moe_gather_kernel<<<capped_grid((R * (d >> 3) + 255) / 256), 256, 0, ST(stream)>>>(R, T, d >> 3, row_token, (const bf16_t*)x, ldx, (bf16_t*)xs, ldxs);
@@ -385,28 +336,34 @@ extern "C" int mi355_moe_gather_rows(int64_t R, int64_t T, int d, const int32_t*
     return 0;
 }
 
+// The one combine launcher (declared in moe_common.h): mi355_moe_combine_fwd and mi355_dsmoe_combine_fwd are this call under their own name.
+int moe_combine_fwd_launch(const char* who, int64_t T, int64_t R, int k, int d, const int32_t* slot, const void* w, const void* y, int64_t ldy, const void* shared,
+                           int64_t lds, const void* residual, int64_t ldr, void* out, int64_t ldo, void* stream) {
+    if (T <= 0) return 0;
+    MI355_REQUIRE(k >= 1 && k <= MOE_MAX_K, "%s: top_k must be in 1..%d (got %d)", who, MOE_MAX_K, k);
+    if (check_rows(who, T, d, {ldo}) || check_rows(who, R, d, {ldy})) return 1;
+    if (shared && check_rows(who, T, d, {lds})) return 1;
+    if (residual && check_rows(who, T, d, {ldr})) return 1;
+    MI355_REQUIRE(R > 0, "%s: the sorted rows must be positive (got %ld)", who, (long)R);
+    MI355_REQUIRE(slot && y && out, "%s: null pointer", who);
+    MI355_REQUIRE(aligned16({y, shared, residual, out}), "%s: y, shared, residual and out must be 16-byte aligned", who);
+    moe_combine_fwd_kernel<<<capped_grid((T * (d >> 3) + 255) / 256), 256, 0, ST(stream)>>>(T, R, k, d >> 3, slot, (const bf16_t*)w, (const bf16_t*)y, ldy,
+                                                                                               (const bf16_t*)shared, lds, (const bf16_t*)residual, ldr, (bf16_t*)out, ldo);
+    MI355_LAUNCH_CHECK(who);
+    return 0;
+}
+
 extern "C" int mi355_moe_combine_fwd(int64_t T, int64_t R, int k, int d, const int32_t* slot, const void* w, const void* y, int64_t ldy, const void* residual,
                                      int64_t ldr, void* out, int64_t ldo, void* stream) {
-    if (T <= 0) return 0;
-    MI355_REQUIRE(k >= 1 && k <= MOE_MAX_K, "mi355_moe_combine_fwd: top_k must be in 1..%d (got %d)", MOE_MAX_K, k);
-    if (check_rows("mi355_moe_combine_fwd", d, {ldy, ldo})) return 1;
-    if (residual && check_rows("mi355_moe_combine_fwd", d, {ldr})) return 1;
-    MI355_REQUIRE(R > 0 && R < (int64_t)1 << 31 && T < (int64_t)1 << 31, "mi355_moe_combine_fwd: row counts must be positive and below 2^31");
-    MI355_REQUIRE(slot && y && out, "mi355_moe_combine_fwd: null pointer");
-    MI355_REQUIRE(aligned16({y, residual, out}), "mi355_moe_combine_fwd: y, residual and out must be 16-byte aligned");
-    moe_combine_fwd_kernel<<<capped_grid((T * (d >> 3) + 255) / 256), 256, 0, ST(stream)>>>(T, R, k, d >> 3, slot, (const bf16_t*)w, (const bf16_t*)y, ldy,
-                                                                                               (const bf16_t*)residual, ldr, (bf16_t*)out, ldo);
-    MI355_LAUNCH_CHECK("mi355_moe_combine_fwd");
-    return 0;
+    return moe_combine_fwd_launch("mi355_moe_combine_fwd", T, R, k, d, slot, w, y, ldy, nullptr, 0, residual, ldr, out, ldo, stream);
 }
 
 extern "C" int mi355_moe_combine_bwd(int64_t T, int64_t R, int k, int d, const int32_t* row_token, const int32_t* slot, const void* w, const void* dout, int64_t ldd,
                                      const void* y, int64_t ldy, void* dy, int64_t lddy, float* dw, void* stream) {
     if (T <= 0 || R <= 0) return 0;
     MI355_REQUIRE(k >= 1 && k <= MOE_MAX_K, "mi355_moe_combine_bwd: top_k must be in 1..%d (got %d)", MOE_MAX_K, k);
-    if (check_rows("mi355_moe_combine_bwd", d, {ldd, lddy})) return 1;
-    if (dw && check_rows("mi355_moe_combine_bwd", d, {ldy})) return 1;
-    MI355_REQUIRE(R < (int64_t)1 << 31 && T < (int64_t)1 << 31, "mi355_moe_combine_bwd: row counts must stay below 2^31");
+    if (check_rows("mi355_moe_combine_bwd", T, d, {ldd}) || check_rows("mi355_moe_combine_bwd", R, d, {lddy})) return 1;
+    if (dw && check_rows("mi355_moe_combine_bwd", R, d, {ldy})) return 1;
     MI355_REQUIRE(row_token && slot && dout && dy && (!dw || y), "mi355_moe_combine_bwd: null pointer");
     MI355_REQUIRE(aligned16({dout, y, dy}), "mi355_moe_combine_bwd: dout, y and dy must be 16-byte aligned");
     moe_combine_bwd_kernel<<<capped_grid((R + 3) / 4), 256, 0, ST(stream)>>>(T, R, k, d >> 3, row_token, slot, (const bf16_t*)w, (const bf16_t*)dout, ldd,

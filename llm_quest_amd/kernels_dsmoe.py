@@ -1,15 +1,16 @@
-"""Tensor-level launchers of the DeepSeekMoE kernels (csrc/deepseek_moe.hip): bias-balanced router, bias update, the shared experts' bias + SiLU,
-the combine that takes the shared experts' output and the fixed-order column sums of the bias gradients; no autograd here.
+"""Tensor-level launchers of the DeepSeekMoE kernels (csrc/deepseek_moe.hip): bias-balanced router, bias update, the shared experts' bias + SiLU
+and the fixed-order column sums of the bias gradients; no autograd here.
 
-Written like ``kernels_moe.py``, whose plan / dispatch / combine-backward / router-backward launchers serve this layer unchanged: every launcher
-checks shapes / strides / dtypes on the host before a pointer reaches the GPU and enqueues on torch's current stream.  There is no CPU fallback.
+Written like ``kernels_moe.py``, whose plan / dispatch / combine / combine-backward / router-backward launchers serve this layer too (the combine that
+takes the shared experts' output is ``kernels_moe.combine_fwd(..., shared=...)``): every launcher checks shapes / strides / dtypes on the host before a
+pointer reaches the GPU and enqueues on torch's current stream.  There is no CPU fallback.
 ``E`` is the number of ROUTED experts, any value in 1..128.
 """
 
 import torch
 
 from . import _lib as L
-from .kernels_moe import MAX_TOP_K, _flat, _gate_rows, _ld, _rows, check_route
+from .kernels_moe import _flat, _gate_rows, _ld, _rows, check_route
 
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
@@ -81,28 +82,6 @@ def bias_silu_bwd(pre, dact):
     dpre = torch.empty((T, N), dtype=BF16, device=pre.device)
     L.call("mi355_dsmoe_bias_silu_bwd", T, N, L.ptr(pre), _ld(pre), L.ptr(dact), _ld(dact), L.ptr(dpre), _ld(dpre))
     return dpre
-
-
-def combine_fwd(y, slot, w, shared=None, residual=None, out=None):
-    """out[t] = residual[t] + shared[t] + sum_j w[t, j] * y[slot[t, j]], fp32, one rounding."""
-    L.require_gpu(y, slot, w, shared, residual, out)
-    R, d = y.shape
-    T, k = slot.shape
-    _rows(y, "y", R, d)
-    _flat(slot, "slot", I32, (T, k))
-    if not 1 <= k <= MAX_TOP_K:
-        raise ValueError(f"dsmoe: top_k must be in 1..{MAX_TOP_K}, got {k}")
-    _flat(w, "w", BF16, (T, k))
-    if shared is not None:
-        _rows(shared, "shared", T, d)
-    if residual is not None:
-        _rows(residual, "residual", T, d)
-    if out is None:
-        out = torch.empty((T, d), dtype=BF16, device=y.device)
-    _rows(out, "out", T, d)
-    L.call("mi355_dsmoe_combine_fwd", T, R, k, d, L.ptr(slot), L.ptr(w), L.ptr(y), _ld(y), L.ptr(shared), 0 if shared is None else _ld(shared), L.ptr(residual),
-           0 if residual is None else _ld(residual), L.ptr(out), _ld(out))
-    return out
 
 
 def colsum(x):

@@ -1,5 +1,6 @@
 """Tensor-level launchers of the mixture-of-experts kernels (csrc/moe.hip): router, token-to-expert plan, row dispatch, weighted combine and
-their backwards; no autograd here.
+their backwards; no autograd here.  Both mixture-of-experts layers use them: the combine is one kernel, and ``combine_fwd`` also takes DeepSeekMoE's
+shared experts' output (``kernels_dsmoe.py`` holds only what that layer adds).
 
 Written like ``kernels_mla.py``: every launcher checks shapes / strides / dtypes on the host before a pointer reaches the GPU, allocates its
 outputs with torch (or takes them from the caller) and enqueues on torch's current stream.  There is no CPU fallback.
@@ -142,9 +143,13 @@ def gather_rows(x, row_token, out=None):
     return out
 
 
-def combine_fwd(y, slot, w=None, residual=None, out=None):
-    """out[t] = residual[t] + sum_j w[t, j] * y[slot[t, j]]; ``w`` None: weights of 1 (the backward of ``gather_rows``)."""
-    L.require_gpu(y, slot, w, residual, out)
+def combine_fwd(y, slot, w=None, residual=None, out=None, shared=None):
+    """out[t] = residual[t] + (shared[t] + sum_j w[t, j] * y[slot[t, j]]), fp32, one rounding; ``w`` None: weights of 1 (the backward of
+    ``gather_rows``).  One kernel behind two entry points: ``shared`` (DeepSeekMoE's shared experts' output, which needs ``w``) goes through
+    ``mi355_dsmoe_combine_fwd``, everything else through ``mi355_moe_combine_fwd``."""
+    if shared is not None and w is None:
+        raise ValueError("moe: the combine with a shared operand needs the weights w")
+    L.require_gpu(y, slot, w, residual, out, shared)
     R, d = y.shape
     T, k = slot.shape
     _rows(y, "y", R, d)
@@ -158,8 +163,12 @@ def combine_fwd(y, slot, w=None, residual=None, out=None):
     if out is None:
         out = torch.empty((T, d), dtype=BF16, device=y.device)
     _rows(out, "out", T, d)
-    L.call("mi355_moe_combine_fwd", T, R, k, d, L.ptr(slot), L.ptr(w), L.ptr(y), _ld(y), L.ptr(residual), 0 if residual is None else _ld(residual),
-           L.ptr(out), _ld(out))
+    tail = (L.ptr(residual), 0 if residual is None else _ld(residual), L.ptr(out), _ld(out))
+    if shared is None:
+        L.call("mi355_moe_combine_fwd", T, R, k, d, L.ptr(slot), L.ptr(w), L.ptr(y), _ld(y), *tail)
+    else:
+        _rows(shared, "shared", T, d)
+        L.call("mi355_dsmoe_combine_fwd", T, R, k, d, L.ptr(slot), L.ptr(w), L.ptr(y), _ld(y), L.ptr(shared), _ld(shared), *tail)
     return out
 
 

@@ -1,12 +1,12 @@
 """Autograd layer of the DeepSeekMoE path: the layer (``DeepSeekMoE``) and the DeepSeek-V3 block that holds one, as ONE node each.
 
-Same construction as ``ops_moe.py``, whose pieces it shares: the routed experts' products run as segmented GEMMs (``ops_moe.experts_forward`` /
-``experts_backward``: gate-up + SwiGLU, ``lin2``, the two dgrads and the two weight gradients are one launch each over all routed experts, the plan's
+Same construction as ``ops_moe.py``, which owns the routed experts' part: ``ops_moe.run_experts_forward`` / ``run_experts_backward`` run the products as
+segmented GEMMs (gate-up + SwiGLU, ``lin2``, the two dgrads and the two weight gradients are one launch each over all routed experts, the plan's
 ``counts`` / ``offsets`` read on the device), so the layer's forward and backward contain no device-to-host read and their launch count does not grow with
-the number of experts; ``MI355_MOE_SEGMENTED=0`` keeps the per-expert path (one host read of the counts, two or three launches per expert).  Plan, row
-dispatch, combine backward and router backward are ``csrc/moe.hip``; the bias-balanced router, the bias update, the shared experts' bias + SiLU, the
-combine that takes the shared output and the fixed-order column sums of the bias gradients are ``csrc/deepseek_moe.hip`` (launchers
-``kernels_dsmoe.py``).
+the number of experts; ``MI355_MOE_SEGMENTED=0`` (``ops_moe.SEGMENTED``) takes the per-expert path there (one host read of the counts, two or three
+launches per expert).  Plan, row dispatch, combine (one kernel; the shared experts' output is its optional addend), combine backward and router backward
+are ``csrc/moe.hip`` (launchers ``kernels_moe.py``); the bias-balanced router, the bias update, the shared experts' bias + SiLU and the fixed-order column
+sums of the bias gradients are ``csrc/deepseek_moe.hip`` (launchers ``kernels_dsmoe.py``).
 
 Two layout points:
   * a routed expert is lin2(silu(lin1(x)) * lin_gate(x)): the SiLU sits on ``lin1``.  The fused gate-up kernels compute u * silu(g) on [u | g], so
@@ -128,33 +128,6 @@ def _flush(wg):
 
 
 # ----------------------------------------------------------------------------------------------- the layer
-def _experts_forward_loop(moe, arena, xs, counts, F_):
-    """The per-expert path (``ops_moe.SEGMENTED`` off): the host reads the counts, then two or three launches per routed expert that received tokens."""
-    n_rows = counts.tolist()  # the device-to-host read the segmented path does without
-    align = KM.row_align()
-    y = torch.empty_like(xs)  # padding rows are never read: the combine kernels go through slot / row_token
-    fused = ops.FUSE_SWIGLU_FWD and F_ % 32 == 0
-    segs, gus, acts, off = [], [], [], 0
-    for e, n in enumerate(n_rows):
-        segs.append((off, n))
-        if n == 0:
-            gus.append(None)
-            acts.append(None)
-            continue
-        ex = moe.routed_experts[e]
-        wgu = arena.fused(ex.lin_gate.weight, ex.lin1.weight)  # [u | g] = [lin_gate | lin1]: a = lin_gate(x) * silu(lin1(x))
-        if fused:
-            gu, a = K.gemm_gateup_swiglu(xs[off : off + n], wgu)
-        else:
-            gu = K.gemm(L.GEMM_NT, xs[off : off + n], wgu)
-            a = K.swiglu_fwd(gu, F_)
-        K.gemm(L.GEMM_NT, a, ex.lin2.weight, out=y[off : off + n])
-        gus.append(gu)
-        acts.append(a)
-        off += (n + align - 1) // align * align
-    return y, gus, acts, segs
-
-
 def moe_forward(moe, arena, h, residual, keep):
     """h bf16 [T, d] contiguous -> residual + shared(h) + routed(h) [T, d]; updates ``moe.biases`` and sets ``moe.max_vio`` on the device."""
     E, k, F_ = moe.num_routed, moe.top_k, moe.routed_experts[0].hidden_dim
@@ -167,41 +140,14 @@ def moe_forward(moe, arena, h, residual, keep):
     object.__setattr__(moe, "max_vio", max_vio.reshape(()))
     object.__setattr__(moe, "_routed", (idx, counts))  # this forward's selection and counts, device tensors (tests and metrics; nothing here reads them back)
     xs = KM.gather_rows(h, row_token)
-    if ops_moe.SEGMENTED:  # every product once over all routed experts, the segment table read on the device (ops_moe.experts_forward)
-        st = ops_moe.expert_stacks(moe, arena, moe.routed_experts, "lin_gate", "lin1")  # [u | g] = [lin_gate | lin1]: a = lin_gate(x) * silu(lin1(x))
-        gus, acts, y = ops_moe.experts_forward(st, xs, counts, offsets, T * k, F_)
-        segs = None
-    else:
-        y, gus, acts, segs = _experts_forward_loop(moe, arena, xs, counts, F_)
+    # [u | g] = [lin_gate | lin1]: a = lin_gate(x) * silu(lin1(x)); segmented or per expert as ops_moe.SEGMENTED says
+    y, gus, acts, segs = ops_moe.run_experts_forward(moe, arena, moe.routed_experts, "lin_gate", "lin1", xs, counts, offsets, T * k, F_)
     sh_out, sh_saved = (None, None)
     if moe.num_shared > 0:
         sh_out, sh_saved = shared_forward(moe.shared_experts, h, keep)
-    out = KD.combine_fwd(y, slot, w, sh_out, residual)
+    out = KM.combine_fwd(y, slot, w, residual, shared=sh_out)
     saved = (h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, offsets, wg8, sh_saved) if keep else None
     return out, saved
-
-
-def _experts_backward_loop(moe, arena, xs, gus, acts, segs, dy, F_, wg):
-    """The per-expert path's d(xs): the forward's segment lengths again, the weight gradients recorded in ``wg``."""
-    dxs = torch.empty_like(xs)
-    for e, (off, n) in enumerate(segs):
-        ex = moe.routed_experts[e]
-        if n == 0:  # no token: a defined, exactly zero gradient (upstream leaves None)
-            for first, last in ((ex.lin_gate.weight, ex.lin1.weight), (ex.lin2.weight, None)):
-                if first.requires_grad:
-                    view, acc = arena.grad_target(first, last)
-                    if not acc:
-                        view.zero_()
-            continue
-        dy_e, gu, a = dy[off : off + n], gus[e], acts[e]
-        if ops.FUSE_SWIGLU_BWD:
-            dgu = K.gemm_dgrad_swiglu_bwd(dy_e, ex.lin2.weight, gu)
-        else:
-            dgu = K.swiglu_bwd(gu, K.dgrad(dy_e, ex.lin2.weight), F_)
-        ops._wgrad(arena, ex.lin2.weight, None, dy_e, a, wg)
-        K.dgrad(dgu, arena.fused(ex.lin_gate.weight, ex.lin1.weight), out=dxs[off : off + n])
-        ops._wgrad(arena, ex.lin_gate.weight, ex.lin1.weight, dgu, xs[off : off + n], wg)
-    return dxs
 
 
 def moe_backward(moe, arena, saved, dout, wg):
@@ -210,11 +156,7 @@ def moe_backward(moe, arena, saved, dout, wg):
     E, F_ = moe.num_routed, moe.routed_experts[0].hidden_dim
     T = h.shape[0]
     dy, dw = KM.combine_bwd(dout, row_token, slot, w, y)
-    if segs is None:  # the forward ran segmented: gus / acts are the whole sorted buffers
-        st = ops_moe.expert_stacks(moe, arena, moe.routed_experts, "lin_gate", "lin1")
-        dxs = ops_moe.experts_backward(st, arena, xs, gus, acts, dy, counts, offsets, T * moe.top_k, F_)
-    else:
-        dxs = _experts_backward_loop(moe, arena, xs, gus, acts, segs, dy, F_, wg)
+    dxs = ops_moe.run_experts_backward(moe, arena, moe.routed_experts, "lin_gate", "lin1", xs, gus, acts, segs, dy, counts, offsets, T * moe.top_k, F_, wg)
     dh = KM.combine_fwd(dxs, slot)  # the gather's backward
     # the gate: dlogits on the padded pitch (pad columns zero), dgrad on the padded weight, the weight gradient through an fp32 scratch
     Ep = wg8.shape[0]

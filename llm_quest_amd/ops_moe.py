@@ -12,6 +12,10 @@ backwards -- is ``csrc/moe.hip`` (launchers ``kernels_moe.py``).
 reads the ``E`` counts once per forward, then runs two or three launches per expert that received tokens; its weight gradients go through the
 caller's grouped launches.  Per segment both paths compute the same sums (the segmented kernels are bit-identical to the per-expert calls on the
 128x128 tile).
+
+This module owns the experts' part of BOTH mixture-of-experts layers: the stacks, the segmented launches, the per-expert loops and the choice between
+the two paths (``run_experts_forward`` / ``run_experts_backward``) take the expert list and the names of the fused pair's two halves, so ``ops_dsmoe.py``
+(routed experts, ``lin_gate`` before ``lin1``) and the two bench tools call them and restate nothing.
 """
 
 import os
@@ -87,6 +91,72 @@ def experts_backward(st, arena, xs, gu, a, dy, counts, offsets, max_rows, F_):
     return dxs
 
 
+# ----------------------------------------------------------------------------------------------- the per-expert path, and the choice between the two
+def _experts_forward_loop(experts, up, gate, arena, xs, n_rows, F_):
+    """The per-expert path (``SEGMENTED`` off): two or three launches per expert that received tokens.  ``n_rows``: the counts as a host list (the layer's
+    device-to-host read); ``experts, up, gate`` as for ``expert_stacks``.  Returns (y, gus, acts, segs)."""
+    align = KM.row_align()
+    y = torch.empty_like(xs)  # rows no expert writes (padding) are never read: the combine kernels go through slot / row_token
+    fused = ops.FUSE_SWIGLU_FWD and F_ % 32 == 0
+    segs, gus, acts, off = [], [], [], 0
+    for ex, n in zip(experts, n_rows):
+        segs.append((off, n))
+        if n == 0:
+            gus.append(None)
+            acts.append(None)
+            continue
+        wgu = arena.fused(getattr(ex, up).weight, getattr(ex, gate).weight)
+        if fused:  # the activation is the projection's epilogue (gu is still written: the backward needs it)
+            gu, a = K.gemm_gateup_swiglu(xs[off : off + n], wgu)
+        else:
+            gu = K.gemm(L.GEMM_NT, xs[off : off + n], wgu)
+            a = K.swiglu_fwd(gu, F_)
+        K.gemm(L.GEMM_NT, a, ex.lin2.weight, out=y[off : off + n])
+        gus.append(gu)
+        acts.append(a)
+        off += (n + align - 1) // align * align
+    return y, gus, acts, segs
+
+
+def _experts_backward_loop(experts, up, gate, arena, xs, gus, acts, segs, dy, F_, wg):
+    """The per-expert path's d(xs): the forward's segment lengths again, the weight gradients recorded in ``wg`` for the caller's grouped launches."""
+    dxs = torch.empty_like(xs)  # as y: only the rows in use are read back
+    for ex, (off, n), gu, a in zip(experts, segs, gus, acts):
+        first, last = getattr(ex, up).weight, getattr(ex, gate).weight
+        if n == 0:  # no token: a defined, exactly zero gradient (upstream leaves None; the optimizer and the gradient sync need the buffer)
+            for lo, hi in ((first, last), (ex.lin2.weight, None)):
+                if lo.requires_grad:
+                    view, acc = arena.grad_target(lo, hi)
+                    if not acc:
+                        view.zero_()
+            continue
+        dy_e = dy[off : off + n]
+        if ops.FUSE_SWIGLU_BWD:  # the activation's backward is the dgrad GEMM's epilogue
+            dgu = K.gemm_dgrad_swiglu_bwd(dy_e, ex.lin2.weight, gu)
+        else:
+            dgu = K.swiglu_bwd(gu, K.dgrad(dy_e, ex.lin2.weight), F_)
+        ops._wgrad(arena, ex.lin2.weight, None, dy_e, a, wg)
+        K.dgrad(dgu, arena.fused(first, last), out=dxs[off : off + n])
+        ops._wgrad(arena, first, last, dgu, xs[off : off + n], wg)
+    return dxs
+
+
+def run_experts_forward(owner, arena, experts, up, gate, xs, counts, offsets, max_rows, F_):
+    """All experts on the sorted rows ``xs``, on the path ``SEGMENTED`` (read here, at call time) selects.  Returns (y, gus, acts, segs), what the layers
+    save: ``segs`` None = segmented (gus / acts are the whole sorted buffers), else the per-expert path's segment list."""
+    if SEGMENTED:  # every product once over all experts, the segment table read on the device: no host read, no per-expert launch
+        gus, acts, y = experts_forward(expert_stacks(owner, arena, experts, up, gate), xs, counts, offsets, max_rows, F_)
+        return y, gus, acts, None
+    return _experts_forward_loop(experts, up, gate, arena, xs, counts.tolist(), F_)  # the device-to-host read the segmented path does without
+
+
+def run_experts_backward(owner, arena, experts, up, gate, xs, gus, acts, segs, dy, counts, offsets, max_rows, F_, wg):
+    """d(xs) [R, d] on the path the forward took.  Segmented, the experts' weight gradients go straight into the arena; per expert they are recorded in ``wg``."""
+    if segs is None:
+        return experts_backward(expert_stacks(owner, arena, experts, up, gate), arena, xs, gus, acts, dy, counts, offsets, max_rows, F_)
+    return _experts_backward_loop(experts, up, gate, arena, xs, gus, acts, segs, dy, F_, wg)
+
+
 # ----------------------------------------------------------------------------------------------- the layer
 def _gate_input(moe, h, gate_probas):
     """The router's input: the gate's logits [T, E] (a column slice of a buffer whose pitch is a multiple of 8), or the replayed probabilities
@@ -106,33 +176,6 @@ def _gate_input(moe, h, gate_probas):
     return K.cast(gp.contiguous(), BF16), True
 
 
-def _experts_forward_loop(moe, arena, xs, counts, F_):
-    """The per-expert path (``SEGMENTED`` off): the host reads the counts, then two or three launches per expert that received tokens."""
-    n_rows = counts.tolist()  # the device-to-host read the segmented path does without: the per-expert launches need the segment lengths
-    align = KM.row_align()
-    y = torch.empty_like(xs)  # rows no expert writes (padding) are never read: the combine kernels go through slot / row_token
-    fused = ops.FUSE_SWIGLU_FWD and F_ % 32 == 0
-    segs, gus, acts, off = [], [], [], 0
-    for e, n in enumerate(n_rows):
-        segs.append((off, n))
-        if n == 0:
-            gus.append(None)
-            acts.append(None)
-            continue
-        ex = moe.experts[e]
-        wgu = arena.fused(ex.lin1.weight, ex.lin_gate.weight)
-        if fused:  # the activation is the projection's epilogue (gu is still written: the backward needs it)
-            gu, a = K.gemm_gateup_swiglu(xs[off : off + n], wgu)
-        else:
-            gu = K.gemm(L.GEMM_NT, xs[off : off + n], wgu)
-            a = K.swiglu_fwd(gu, F_)
-        K.gemm(L.GEMM_NT, a, ex.lin2.weight, out=y[off : off + n])
-        gus.append(gu)
-        acts.append(a)
-        off += (n + align - 1) // align * align
-    return y, gus, acts, segs
-
-
 def moe_forward(moe, arena, h, residual, gate_probas, keep):
     """h bf16 [T, d] contiguous -> (residual + moe(h) [T, d], load loss fp32 [1] or None, the probabilities routed by, saved or None)."""
     E, k, F_ = moe.num_experts, moe.top_k, moe.experts[0].hidden_dim
@@ -142,38 +185,10 @@ def moe_forward(moe, arena, h, residual, gate_probas, keep):
     psum = K.colsum(p) if moe.training else None
     counts, offsets, slot, row_token, loss = KM.plan(idx, E, psum, moe.load_coeff)
     xs = KM.gather_rows(h, row_token)
-    if SEGMENTED:  # every product once over all experts, the segment table read on the device: no host read, no per-expert launch
-        st = expert_stacks(moe, arena, moe.experts, "lin1", "lin_gate")
-        gus, acts, y = experts_forward(st, xs, counts, offsets, T * k, F_)
-        segs = None
-    else:
-        y, gus, acts, segs = _experts_forward_loop(moe, arena, xs, counts, F_)
+    y, gus, acts, segs = run_experts_forward(moe, arena, moe.experts, "lin1", "lin_gate", xs, counts, offsets, T * k, F_)
     out = KM.combine_fwd(y, slot, w, residual)
     saved = (h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, offsets, replay) if keep else None
     return out, loss, p, saved
-
-
-def _experts_backward_loop(moe, arena, xs, gus, acts, segs, dy, F_, wg):
-    """The per-expert path's d(xs): the forward's segment lengths again, the weight gradients recorded in ``wg``."""
-    dxs = torch.empty_like(xs)  # as y: only the rows in use are read back
-    for e, (off, n) in enumerate(segs):
-        ex = moe.experts[e]
-        if n == 0:  # no token: a defined, exactly zero gradient (upstream leaves None; the optimizer and the gradient sync need the buffer)
-            for first, last in ((ex.lin1.weight, ex.lin_gate.weight), (ex.lin2.weight, None)):
-                if first.requires_grad:
-                    view, acc = arena.grad_target(first, last)
-                    if not acc:
-                        view.zero_()
-            continue
-        dy_e, gu, a = dy[off : off + n], gus[e], acts[e]
-        if ops.FUSE_SWIGLU_BWD:  # the activation's backward is the dgrad GEMM's epilogue
-            dgu = K.gemm_dgrad_swiglu_bwd(dy_e, ex.lin2.weight, gu)
-        else:
-            dgu = K.swiglu_bwd(gu, K.dgrad(dy_e, ex.lin2.weight), F_)
-        ops._wgrad(arena, ex.lin2.weight, None, dy_e, a, wg)
-        K.dgrad(dgu, arena.fused(ex.lin1.weight, ex.lin_gate.weight), out=dxs[off : off + n])
-        ops._wgrad(arena, ex.lin1.weight, ex.lin_gate.weight, dgu, xs[off : off + n], wg)
-    return dxs
 
 
 def moe_backward(moe, arena, saved, dout, g_loss, wg):
@@ -182,11 +197,7 @@ def moe_backward(moe, arena, saved, dout, g_loss, wg):
     h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, offsets, replay = saved
     F_ = moe.experts[0].hidden_dim
     dy, dw = KM.combine_bwd(dout, row_token, slot, w, None if replay else y)
-    if segs is None:  # the forward ran segmented: gus / acts are the whole sorted buffers
-        st = expert_stacks(moe, arena, moe.experts, "lin1", "lin_gate")
-        dxs = experts_backward(st, arena, xs, gus, acts, dy, counts, offsets, h.shape[0] * moe.top_k, F_)
-    else:
-        dxs = _experts_backward_loop(moe, arena, xs, gus, acts, segs, dy, F_, wg)
+    dxs = run_experts_backward(moe, arena, moe.experts, "lin1", "lin_gate", xs, gus, acts, segs, dy, counts, offsets, h.shape[0] * moe.top_k, F_, wg)
     dh = KM.combine_fwd(dxs, slot)  # the gather's backward: dh[t] = sum_j dxs[slot[t, j]]
     if not replay:  # a replayed routing is a constant: the gate is not evaluated and gets no gradient
         dlogits = KM.route_bwd(dw, w, s, idx, p, counts, g_loss, moe.load_coeff)

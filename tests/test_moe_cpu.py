@@ -259,3 +259,9 @@ def test_launchers_check_shapes_before_the_library_is_called():
     with pytest.raises(ValueError, match="2\\^31"):
         KM.check_route(2 ** 30, 8, 8)
     KM.check_route(130, 128, 8)
+    # the combine's shared operand (DeepSeekMoE) needs the weights: refused on plain CPU tensors, before the device is asked for
+    y, slot = torch.zeros(8, 64, dtype=BF16), torch.zeros(4, 2, dtype=torch.int32)
+    with pytest.raises(ValueError, match="shared operand needs the weights"):
+        KM.combine_fwd(y, slot, shared=torch.zeros(4, 64, dtype=BF16))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):  # with the weights the call goes on to the device check
+        KM.combine_fwd(y, slot, torch.zeros(4, 2, dtype=BF16), shared=torch.zeros(4, 64, dtype=BF16))

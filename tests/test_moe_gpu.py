@@ -172,6 +172,7 @@ def test_gather_combine_and_combine_backward_against_fp64(d, sliced):
     rn = lambda *s: torch.randn(*s, generator=g).to(BF16)
     x, y, res, dout = rn(T, d), rn(R, d), rn(T, d), rn(T, d)
     w = torch.rand(T, k, generator=g).to(BF16)
+    shared = rn(T, d)  # (drawn last: the operands above keep their values)
     y_dev = y.clone()
     y_dev[~used] = float("nan")  # rows no expert writes: never read
     put = (lambda t: _slice_of(t.cuda())) if sliced else (lambda t: t.cuda())
@@ -185,12 +186,14 @@ def test_gather_combine_and_combine_backward_against_fp64(d, sliced):
     assert torch.equal(xs.cpu(), want)
 
     # combine, the weighted form with the residual: fp64 against the bf16 flow (every product and every add rounded)
-    def combine(dtype, weights, residual):
+    def combine(dtype, weights, residual, shared=None):
         c = (lambda t: t) if dtype is None else (lambda t: t.to(dtype))
         out = torch.zeros(T, d, dtype=BF16 if dtype is None else dtype)
         for j in range(k):
             rows = c(y)[sl[:, j]]
             out = out + (rows * c(weights)[:, j : j + 1] if weights is not None else rows)
+        if shared is not None:
+            out = out + c(shared)
         return out + c(residual) if residual is not None else out
 
     out = KM.combine_fwd(put(y_dev), slot, w.cuda(), put(res), out=dest(T))
@@ -200,6 +203,12 @@ def test_gather_combine_and_combine_backward_against_fp64(d, sliced):
     # w = NULL: the gather's backward, dx[t] = sum_j dxs[slot[t, j]]
     out_sum = KM.combine_fwd(put(y_dev), slot, out=dest(T))
     judge("combine, w = NULL", out_sum, combine(None, None, None), combine(torch.float64, None, None), bad)
+    # the shared experts' addend (DeepSeekMoE: the same kernel behind mi355_dsmoe_combine_fwd): residual + (shared + sum_j w_j y_j)
+    out_sh = KM.combine_fwd(put(y_dev), slot, w.cuda(), put(res), out=dest(T), shared=put(shared))
+    judge("combine, shared and residual", out_sh, combine(None, w, res, shared), combine(torch.float64, w, res, shared), bad)
+    # ... and it is the only difference between the two entry points: a zero addend changes no bit (x + 0 = x; a sum that is -0 reads back equal to +0)
+    out_sh0 = KM.combine_fwd(put(y_dev), slot, w.cuda(), put(res), out=dest(T), shared=put(torch.zeros_like(shared)))
+    assert torch.equal(out_sh0, out)
 
     # combine backward: dy = w(r) * dout[token(r)] (zeros on padding rows), dw = <dout[t], y[slot[t, j]]>
     dy, dw = KM.combine_bwd(put(dout), row_token, slot, w.cuda(), put(y_dev), dy=dest(R))

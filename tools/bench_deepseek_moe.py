@@ -4,8 +4,8 @@
 
 One DeepSeekMoE layer of ``DEEPSEEK_SMALL_CONFIG`` (emb 768, 7 routed + 1 shared expert of hidden 768, top_k 3), forward + backward on
 ``--tokens`` tokens, and its split as ``bench_moe.py`` splits: router and bias update (gate GEMM, route forward / backward, the update), plan,
-rows (dispatch, combine and their backwards), shared experts, routed expert GEMMs (per-expert launches on the layer's own counts, the host read
-included, and the six segmented launches).  The layer and the model steps run with ``ops_moe.SEGMENTED`` on and off in this one process: both medians
+rows (dispatch, combine and their backwards), shared experts, routed expert GEMMs (the layer's own per-expert loops of ``ops_moe`` on the layer's own
+counts, the host read included, all forwards then all backwards, and the six segmented launches).  The layer and the model steps run with ``ops_moe.SEGMENTED`` on and off in this one process: both medians
 and their ratio are in the output.  The dense ``FFN`` of the same config (hidden 3072) on the same tokens in the same run.  Then the training step of
 ``DEEPSEEK_SMALL_CONFIG`` as written (3 dense + 9 MoE blocks, mtp_depth 2) beside the all-dense one ``bench_deepseek.py`` measures.
 
@@ -48,7 +48,7 @@ def measure_layer(cfg, T, steps, warmup):
     from llm_quest_amd import kernels as K
     from llm_quest_amd import kernels_dsmoe as KD
     from llm_quest_amd import kernels_moe as KM
-    from llm_quest_amd import ops, ops_dsmoe, ops_moe
+    from llm_quest_amd import ops_dsmoe, ops_moe
     from llm_quest_amd.moe.deepseek_moe import DeepSeekMoE
 
     torch.manual_seed(0)
@@ -103,7 +103,7 @@ def measure_layer(cfg, T, steps, warmup):
 
     def rows():
         KM.gather_rows(h, row_token)
-        KD.combine_fwd(y, slot, w, h, h)
+        KM.combine_fwd(y, slot, w, h, shared=h)
         KM.combine_bwd(dout, row_token, slot, w, y)
         KM.combine_fwd(xs, slot)
 
@@ -115,22 +115,10 @@ def measure_layer(cfg, T, steps, warmup):
 
     F_ = moe.routed_experts[0].hidden_dim
 
-    def experts():
-        n_rows = counts.tolist()  # the host read the layer pays
-        align, off, wg = KM.row_align(), 0, []
-        for e, n in enumerate(n_rows):
-            if n == 0:
-                continue
-            ex = moe.routed_experts[e]
-            wgu = arena.fused(ex.lin_gate.weight, ex.lin1.weight)
-            xe, de = xs[off : off + n], y[off : off + n]
-            gu, a = K.gemm_gateup_swiglu(xe, wgu)
-            K.gemm(L.GEMM_NT, a, ex.lin2.weight)
-            dgu = K.gemm_dgrad_swiglu_bwd(de, ex.lin2.weight, gu)
-            ops._wgrad(arena, ex.lin2.weight, None, de, a, wg)
-            K.dgrad(dgu, wgu)
-            ops._wgrad(arena, ex.lin_gate.weight, ex.lin1.weight, dgu, xe, wg)
-            off += (n + align - 1) // align * align
+    def experts():  # the layer's own per-expert loops (ops_moe): the host read the layer pays, all forwards, then all backwards
+        wg, routed = [], moe.routed_experts
+        _, gus, acts, segs = ops_moe._experts_forward_loop(routed, "lin_gate", "lin1", arena, xs, counts.tolist(), F_)
+        ops_moe._experts_backward_loop(routed, "lin_gate", "lin1", arena, xs, gus, acts, segs, y, F_, wg)
         ops_dsmoe._flush(wg)
 
     st = ops_moe.expert_stacks(moe, arena, moe.routed_experts, "lin_gate", "lin1")

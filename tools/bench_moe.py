@@ -7,7 +7,8 @@ a trained-like gate (gate weights scaled so that the probabilities are peaked; r
   * the whole layer (``ops_moe.MoEFn``), device events around forward + backward, with ``ops_moe.SEGMENTED`` on (segmented GEMMs: one launch per product
     over all experts, no host read) and off (per-expert launches behind the read of the counts): both medians and their ratio, from this one run;
   * its split: the row kernels of csrc/moe.hip alone (route, column sums, plan, gather, combine, their backwards), the expert GEMMs alone (forward + backward
-    with the weight gradients on prepared segments: the per-expert loop, and the six segmented launches), the gate's three GEMMs, and the host's
+    with the weight gradients on prepared segments: the layer's own per-expert loops of ``ops_moe``, all forwards then all backwards, and the six
+    segmented launches), the gate's three GEMMs, and the host's
     wait on the ``E`` counts (host clock around the one device-to-host read, queue drained before the router is enqueued);
   * the dense SwiGLU FFN of the same activated width (hidden = k * F) through the existing kernels, forward + backward;
   * one ``30B-A3B``-shaped layer (d = 2048, F = 768, E = 128, k = 8), both paths: what 128 experts' launches cost.
@@ -120,31 +121,11 @@ def measure_layer(name, d, F_, E, k, T, steps, warmup, split):
 
     out.append(dict(kind="split", name=name, part="row kernels (route, colsum, plan, gather, combine, combine backward, gather backward, route backward)",
                     **time_calls(rows, steps, warmup)))
-    # ---- the expert GEMMs alone: the layer's per-expert loop, forward + backward with the weight gradients
-    align = KM.row_align()
-    segs, off = [], 0
-    for n in n_rows:
-        segs.append((off, n))
-        off += (n + align - 1) // align * align
-    fused = F_ % 32 == 0
-
+    # ---- the expert GEMMs alone: the layer's own per-expert loops (ops_moe) on the counts read above, all forwards, then all backwards with the weight gradients
     def experts():
-        wg, dxs = [], torch.empty_like(xs)
-        for e, (o, n) in enumerate(segs):
-            if n == 0:
-                continue
-            ex = moe.experts[e]
-            wgu = arena.fused(ex.lin1.weight, ex.lin_gate.weight)
-            if fused:
-                gu, a = K.gemm_gateup_swiglu(xs[o : o + n], wgu)
-            else:
-                gu = K.gemm(L.GEMM_NT, xs[o : o + n], wgu)
-                a = K.swiglu_fwd(gu, F_)
-            K.gemm(L.GEMM_NT, a, ex.lin2.weight, out=y[o : o + n])
-            dgu = K.gemm_dgrad_swiglu_bwd(y[o : o + n], ex.lin2.weight, gu)
-            ops._wgrad(arena, ex.lin2.weight, None, y[o : o + n], a, wg)
-            K.dgrad(dgu, wgu, out=dxs[o : o + n])
-            ops._wgrad(arena, ex.lin1.weight, ex.lin_gate.weight, dgu, xs[o : o + n], wg)
+        wg = []
+        _, gus, acts, segs = ops_moe._experts_forward_loop(moe.experts, "lin1", "lin_gate", arena, xs, n_rows, F_)
+        ops_moe._experts_backward_loop(moe.experts, "lin1", "lin_gate", arena, xs, gus, acts, segs, y, F_, wg)
         ops._flush_wgrads(wg)
 
     out.append(dict(kind="split", name=name, part="expert GEMMs, per-expert launches (gate-up + SwiGLU, lin2, their dgrads, grouped weight gradients)",
