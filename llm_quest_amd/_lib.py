@@ -144,6 +144,11 @@ SIGNATURES = {
     "mi355_dsmoe_bias_silu_bwd": [_L, _I, _P, _L, _P, _L, _P, _L, _P],
     "mi355_dsmoe_combine_fwd": [_L, _L, _I, _I, _P, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P],
     "mi355_dsmoe_colsum_parts": [_L, _I, _P, _L, _P, _I, _P],
+    # MiMo-V2-Flash: attention with a sink and its own v head dim, the sink gradient, per-head RMSNorm + partial RoPE (csrc/mimo.hip)
+    "mi355_sink_attn_fwd": [_I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _P, _L, _P, _F, _P],
+    "mi355_sink_attn_bwd": [_I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P, _L, _P, _L, _P, _I, _F, _P],
+    "mi355_mimo_normrope_fwd": [_L, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _L, _P, _L, _F, _P],
+    "mi355_mimo_normrope_bwd": [_L, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _L, _P, _L, _P, _L, _P, _I, _F, _P],
 }
 # size / constant queries: no stream argument, the return value is the answer (name -> (argtypes, restype))
 QUERIES = {
