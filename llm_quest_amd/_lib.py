@@ -144,6 +144,11 @@ SIGNATURES = {
     "mi355_dsmoe_bias_silu_bwd": [_L, _I, _P, _L, _P, _L, _P, _L, _P],
     "mi355_dsmoe_combine_fwd": [_L, _L, _I, _I, _P, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P],
     "mi355_dsmoe_colsum_parts": [_L, _I, _P, _L, _P, _I, _P],
+    # Nemotron-3 LatentMoE: sigmoid router with balancing biases and a scaling factor, squared-ReLU GLU (csrc/latent_moe.hip)
+    "mi355_latmoe_route_fwd": [_L, _I, _I, _P, _L, _P, _I, _P, _F, _P, _L, _P, _P, _P, _P],
+    "mi355_latmoe_route_bwd": [_L, _I, _I, _P, _P, _P, _P, _L, _F, _P, _L, _P],
+    "mi355_latmoe_relu2_glu_fwd": [_L, _I, _P, _L, _P, _L, _P],
+    "mi355_latmoe_relu2_glu_bwd": [_L, _I, _P, _L, _P, _L, _P, _L, _P],
     # MiMo-V2-Flash: attention with a sink and its own v head dim, the sink gradient, per-head RMSNorm + partial RoPE (csrc/mimo.hip)
     "mi355_sink_attn_fwd": [_I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _P, _L, _P, _F, _P],
     "mi355_sink_attn_bwd": [_I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P, _L, _P, _L, _P, _I, _F, _P],

@@ -8,29 +8,14 @@
 //   colsum    column sums of bf16 rows as per-row-part partials in a fixed order (the bias gradients)
 //
 // The plan, the row dispatch, the combine's backward and the router's backward are moe.hip's (mi355_moe_route_bwd takes any E in 1..128); the limits, the
-// host checks and the two ends of the router kernel (the token's softmax, the write-out of s / idx / w) are shared with it through moe_common.h.
+// host checks and the two ends of the router kernel (the token's softmax, the write-out of s / idx / w) are shared with it through moe_common.h, which also
+// holds the bias-balanced selection between them (latent_moe.hip routes with it too).
 // No atomics, one writer per element, fixed summation orders.  Rounding points are the reference's bf16 tensors:
 //   p = bf16(softmax), key = p + biases in the promoted dtype, s = bf16(sum_j v_j), w_j = bf16(v_j / s)     (deepseek_moe.py:180-186)
 //   pre = bf16(bf16(x W1) + b1), act = bf16(silu(pre))                                                        (deepseek_moe.py:82-88, 125-126)
 #include "moe_common.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned wave_umin(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned u = (unsigned)__shfl_xor((int)v, o, 64);
-        v = u < v ? u : v;
-    }
-    return v;
-}
-
-// fp32 bits -> an unsigned that orders like the value; never 0 for a number (0 marks a lane that holds no live expert)
-__device__ __forceinline__ unsigned order_f32(float x) {
-    const unsigned b = __float_as_uint(x);
-    const unsigned o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return o == 0u ? 1u : o;
-}
 
 // ------------------------------------------------------------------------------------------------ route, forward
 // One wave per token; lane l holds experts l and l + 64.  Columns at and beyond E are never read.
@@ -41,11 +26,7 @@ __global__ __launch_bounds__(256) void dsmoe_route_fwd_kernel(int64_t T, int E, 
     const int lane = threadIdx.x & 63;
     const int64_t waves = (int64_t)gridDim.x * 4;
     float bv[2] = {0.f, 0.f};
-    if (!FORCED) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-            if (lane + 64 * h < E) bv[h] = BIAS_F32 ? ((const float*)bias)[lane + 64 * h] : bf2f(((const bf16_t*)bias)[lane + 64 * h]);
-    }
+    if (!FORCED) route_load_bias<BIAS_F32>(bias, E, lane, bv);
     for (int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); t < T; t += waves) {
         bf16_t pb[2];
         float pf[2];
@@ -57,39 +38,7 @@ __global__ __launch_bounds__(256) void dsmoe_route_fwd_kernel(int64_t T, int E, 
         }
         float v[MOE_MAX_K];
         int ex[MOE_MAX_K];
-        float sum = 0.f;
-        if (FORCED) {
-#pragma unroll
-            for (int j = 0; j < MOE_MAX_K; ++j)
-                if (j < k) {
-                    const int f = forced[t * k + j];
-                    const bool ok = f >= 0 && f < E;  // not an expert: weight 0, and mi355_moe_plan gives the assignment no row
-                    const float lo = __shfl(pf[0], ok ? (f & 63) : 0, 64), hi = __shfl(pf[1], ok ? (f & 63) : 0, 64);
-                    ex[j] = f;
-                    v[j] = ok ? (f >= 64 ? hi : lo) : 0.f;
-                    sum += v[j];
-                }
-        } else {
-            unsigned key[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const float kf = BIAS_F32 ? pf[h] + bv[h] : rbf(pf[h] + bv[h]);  // the promoted dtype of p (bf16) and the buffer
-                key[h] = lane + 64 * h < E ? order_f32(kf) : 0u;
-            }
-#pragma unroll
-            for (int j = 0; j < MOE_MAX_K; ++j)
-                if (j < k) {
-                    const unsigned best = wave_umax(key[0] > key[1] ? key[0] : key[1]);
-                    const unsigned mine = (key[0] != 0u && key[0] == best) ? (unsigned)lane : ((key[1] != 0u && key[1] == best) ? (unsigned)(lane + 64) : 255u);
-                    const int sel = (int)wave_umin(mine);  // the lowest expert among equal keys; k <= E keeps one alive
-                    const float lo = __shfl(pf[0], sel & 63, 64), hi = __shfl(pf[1], sel & 63, 64);
-                    ex[j] = sel;
-                    v[j] = sel >= 64 ? hi : lo;
-                    sum += v[j];  // slot order
-                    if (sel == lane) key[0] = 0u;
-                    if (sel == lane + 64) key[1] = 0u;
-                }
-        }
+        const float sum = route_select_biased<BIAS_F32, FORCED>(pf, bv, FORCED ? forced + t * k : nullptr, E, k, lane, ex, v);  // moe_common.h
         route_write(t, k, lane, ex, v, sum, idx, w, s);
     }
 }
@@ -195,8 +144,6 @@ __global__ __launch_bounds__(256) void dsmoe_colsum_parts_kernel(int64_t T, int 
         if (gc < N) parts[(int64_t)blockIdx.y * N + gc] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
     }
 }
-
-bool bias_dtype_ok(int dt) { return dt == MI355_DT_BF16 || dt == MI355_DT_F32; }
 
 }  // namespace
 

@@ -1,6 +1,6 @@
-// What the two mixture-of-experts files (moe.hip, deepseek_moe.hip) share and nobody else uses: the E / k limits, the host checks of their entry
-// points, the two ends of a router kernel (the token's softmax in front of the selection, the write-out behind it) and the declaration of the one
-// combine launcher.  Internal: not installed, no entry point lives here.
+// What the mixture-of-experts files (moe.hip, deepseek_moe.hip, latent_moe.hip) share and nobody else uses: the E / k limits, the host checks of their entry
+// points, the two ends of a router kernel (the token's softmax in front of the selection, the write-out behind it), the bias-balanced selection between them
+// (deepseek_moe.hip and latent_moe.hip) and the declaration of the one combine launcher.  Internal: not installed, no entry point lives here.
 #pragma once
 #include <initializer_list>
 
@@ -53,6 +53,78 @@ __device__ __forceinline__ void route_write(int64_t t, int k, int lane, const in
             }
     }
 }
+
+// ------------------------------------------------------------------------------------------------ the bias-balanced selection (DeepSeekMoE, LatentMoE)
+__device__ __forceinline__ unsigned wave_umin(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned u = (unsigned)__shfl_xor((int)v, o, 64);
+        v = u < v ? u : v;
+    }
+    return v;
+}
+
+// fp32 bits -> an unsigned that orders like the value; never 0 for a number (0 marks a lane that holds no live expert)
+__device__ __forceinline__ unsigned order_f32(float x) {
+    const unsigned b = __float_as_uint(x);
+    const unsigned o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return o == 0u ? 1u : o;
+}
+
+// the lane's two balancing biases as floats (0 beyond E)
+template <bool BIAS_F32>
+__device__ __forceinline__ void route_load_bias(const void* __restrict__ bias, int E, int lane, float (&bv)[2]) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        bv[h] = 0.f;
+        if (lane + 64 * h < E) bv[h] = BIAS_F32 ? ((const float*)bias)[lane + 64 * h] : bf2f(((const bf16_t*)bias)[lane + 64 * h]);
+    }
+}
+
+// Between a token's bf16 probabilities pf (as floats, 0 beyond E) and the write-out: the k experts ex_j and their UNBIASED probabilities v_j; returns their sum in
+// slot order.  The key is pf + bv in the promoted dtype of p and the buffer (a bf16 sum, or fp32 with BIAS_F32); k rounds of a wave maximum over the keys and a wave
+// minimum over the experts that hold it: the lowest expert among equal keys, and k <= E keeps one alive.  FORCED: the token's row of given experts instead
+// (``forced``: its k entries); one that is no expert weighs 0, and mi355_moe_plan gives the assignment no row.
+template <bool BIAS_F32, bool FORCED>
+__device__ __forceinline__ float route_select_biased(const float (&pf)[2], const float (&bv)[2], const int* __restrict__ forced, int E, int k, int lane,
+                                                     int (&ex)[MOE_MAX_K], float (&v)[MOE_MAX_K]) {
+    float sum = 0.f;
+    if (FORCED) {
+#pragma unroll
+        for (int j = 0; j < MOE_MAX_K; ++j)
+            if (j < k) {
+                const int f = forced[j];
+                const bool ok = f >= 0 && f < E;
+                const float lo = __shfl(pf[0], ok ? (f & 63) : 0, 64), hi = __shfl(pf[1], ok ? (f & 63) : 0, 64);
+                ex[j] = f;
+                v[j] = ok ? (f >= 64 ? hi : lo) : 0.f;
+                sum += v[j];
+            }
+    } else {
+        unsigned key[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float kf = BIAS_F32 ? pf[h] + bv[h] : rbf(pf[h] + bv[h]);
+            key[h] = lane + 64 * h < E ? order_f32(kf) : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < MOE_MAX_K; ++j)
+            if (j < k) {
+                const unsigned best = wave_umax(key[0] > key[1] ? key[0] : key[1]);
+                const unsigned mine = (key[0] != 0u && key[0] == best) ? (unsigned)lane : ((key[1] != 0u && key[1] == best) ? (unsigned)(lane + 64) : 255u);
+                const int sel = (int)wave_umin(mine);
+                const float lo = __shfl(pf[0], sel & 63, 64), hi = __shfl(pf[1], sel & 63, 64);
+                ex[j] = sel;
+                v[j] = sel >= 64 ? hi : lo;
+                sum += v[j];  // slot order
+                if (sel == lane) key[0] = 0u;
+                if (sel == lane + 64) key[1] = 0u;
+            }
+    }
+    return sum;
+}
+
+inline bool bias_dtype_ok(int dt) { return dt == MI355_DT_BF16 || dt == MI355_DT_F32; }
 
 // ------------------------------------------------------------------------------------------------ host checks
 inline bool aligned16(std::initializer_list<const void*> ps) {

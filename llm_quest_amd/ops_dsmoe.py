@@ -68,12 +68,12 @@ def _gate_operands(moe):
     return wp, bp
 
 
-def _forced(moe, T):
+def _forced(moe, T, what="DeepSeekMoE"):
     f = getattr(moe, "_forced_topk", None)
     if f is None:
         return None
     if tuple(f.shape) != (T, moe.top_k):
-        raise ValueError(f"DeepSeekMoE: the forced selection must be (tokens, top_k) = {(T, moe.top_k)}, got {tuple(f.shape)}")
+        raise ValueError(f"{what}: the forced selection must be (tokens, top_k) = {(T, moe.top_k)}, got {tuple(f.shape)}")
     return f.to(dtype=I32).contiguous()
 
 

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib as L
 from . import kernels as K
+from . import kernels_latmoe as KL
 from . import kernels_moe as KM
 from . import ops
 
@@ -61,10 +62,20 @@ def expert_stacks(owner, arena, experts, up, gate):
     return st
 
 
-def experts_forward(st, xs, counts, offsets, max_rows, F_):
+def _check_activation(activation):
+    if activation not in ("swiglu", "relu2"):
+        raise ValueError(f"moe: the experts' activation must be 'swiglu' or 'relu2', got {activation!r}")
+    return activation == "relu2"
+
+
+def experts_forward(st, xs, counts, offsets, max_rows, F_, activation="swiglu"):
     """(gu [R, 2F], a [R, F], y [R, d]) of all experts on the sorted rows ``xs``: two launches (three when F % 32 != 0 keeps the unfused SwiGLU kernel, which
-    then runs once over the whole sorted buffer; padding rows hold no defined value and are never read through slot / row_token)."""
-    if ops.FUSE_SWIGLU_FWD and F_ % 32 == 0:
+    then runs once over the whole sorted buffer; padding rows hold no defined value and are never read through slot / row_token).  ``activation``
+    "relu2" (LatentMoE: a = u * relu(g)^2) always takes that unfused route, with ``KL.relu2_glu_fwd`` as the activation kernel."""
+    if _check_activation(activation):
+        gu = K.gemm_segmented(L.GEMM_NT, xs, st.wgu, counts, offsets, max_rows)
+        a = KL.relu2_glu_fwd(gu, F_)
+    elif ops.FUSE_SWIGLU_FWD and F_ % 32 == 0:
         gu, a = K.gemm_segmented(L.GEMM_NT, xs, st.wgu, counts, offsets, max_rows, epilogue="swiglu_fwd")
     else:
         gu = K.gemm_segmented(L.GEMM_NT, xs, st.wgu, counts, offsets, max_rows)
@@ -73,10 +84,13 @@ def experts_forward(st, xs, counts, offsets, max_rows, F_):
     return gu, a, y
 
 
-def experts_backward(st, arena, xs, gu, a, dy, counts, offsets, max_rows, F_):
-    """d(xs) [R, d]; the experts' weight gradients go straight into the arena: two dgrad launches (+ the unfused SwiGLU backward when switched off) and two
-    weight-gradient launches over all experts.  An expert without a token ends with an exactly zero (or, accumulating, unchanged) attached gradient."""
-    if ops.FUSE_SWIGLU_BWD:
+def experts_backward(st, arena, xs, gu, a, dy, counts, offsets, max_rows, F_, activation="swiglu"):
+    """d(xs) [R, d]; the experts' weight gradients go straight into the arena: two dgrad launches (+ the unfused SwiGLU backward when switched off, or the
+    squared-ReLU backward for ``activation`` "relu2") and two weight-gradient launches over all experts.  An expert without a token ends with an exactly
+    zero (or, accumulating, unchanged) attached gradient."""
+    if _check_activation(activation):
+        dgu = KL.relu2_glu_bwd(gu, K.gemm_segmented(L.GEMM_NN, dy, st.w2, counts, offsets, max_rows), F_)
+    elif ops.FUSE_SWIGLU_BWD:
         dgu = K.gemm_segmented(L.GEMM_NN, dy, st.w2, counts, offsets, max_rows, epilogue="swiglu_bwd", second=gu)
     else:
         dgu = K.swiglu_bwd(gu, K.gemm_segmented(L.GEMM_NN, dy, st.w2, counts, offsets, max_rows), F_)
@@ -92,12 +106,13 @@ def experts_backward(st, arena, xs, gu, a, dy, counts, offsets, max_rows, F_):
 
 
 # ----------------------------------------------------------------------------------------------- the per-expert path, and the choice between the two
-def _experts_forward_loop(experts, up, gate, arena, xs, n_rows, F_):
+def _experts_forward_loop(experts, up, gate, arena, xs, n_rows, F_, activation="swiglu"):
     """The per-expert path (``SEGMENTED`` off): two or three launches per expert that received tokens.  ``n_rows``: the counts as a host list (the layer's
     device-to-host read); ``experts, up, gate`` as for ``expert_stacks``.  Returns (y, gus, acts, segs)."""
     align = KM.row_align()
     y = torch.empty_like(xs)  # rows no expert writes (padding) are never read: the combine kernels go through slot / row_token
-    fused = ops.FUSE_SWIGLU_FWD and F_ % 32 == 0
+    relu2 = _check_activation(activation)
+    fused = ops.FUSE_SWIGLU_FWD and F_ % 32 == 0 and not relu2
     segs, gus, acts, off = [], [], [], 0
     for ex, n in zip(experts, n_rows):
         segs.append((off, n))
@@ -110,7 +125,7 @@ def _experts_forward_loop(experts, up, gate, arena, xs, n_rows, F_):
             gu, a = K.gemm_gateup_swiglu(xs[off : off + n], wgu)
         else:
             gu = K.gemm(L.GEMM_NT, xs[off : off + n], wgu)
-            a = K.swiglu_fwd(gu, F_)
+            a = KL.relu2_glu_fwd(gu, F_) if relu2 else K.swiglu_fwd(gu, F_)
         K.gemm(L.GEMM_NT, a, ex.lin2.weight, out=y[off : off + n])
         gus.append(gu)
         acts.append(a)
@@ -118,8 +133,9 @@ def _experts_forward_loop(experts, up, gate, arena, xs, n_rows, F_):
     return y, gus, acts, segs
 
 
-def _experts_backward_loop(experts, up, gate, arena, xs, gus, acts, segs, dy, F_, wg):
+def _experts_backward_loop(experts, up, gate, arena, xs, gus, acts, segs, dy, F_, wg, activation="swiglu"):
     """The per-expert path's d(xs): the forward's segment lengths again, the weight gradients recorded in ``wg`` for the caller's grouped launches."""
+    relu2 = _check_activation(activation)
     dxs = torch.empty_like(xs)  # as y: only the rows in use are read back
     for ex, (off, n), gu, a in zip(experts, segs, gus, acts):
         first, last = getattr(ex, up).weight, getattr(ex, gate).weight
@@ -131,7 +147,9 @@ def _experts_backward_loop(experts, up, gate, arena, xs, gus, acts, segs, dy, F_
                         view.zero_()
             continue
         dy_e = dy[off : off + n]
-        if ops.FUSE_SWIGLU_BWD:  # the activation's backward is the dgrad GEMM's epilogue
+        if relu2:
+            dgu = KL.relu2_glu_bwd(gu, K.dgrad(dy_e, ex.lin2.weight), F_)
+        elif ops.FUSE_SWIGLU_BWD:  # the activation's backward is the dgrad GEMM's epilogue
             dgu = K.gemm_dgrad_swiglu_bwd(dy_e, ex.lin2.weight, gu)
         else:
             dgu = K.swiglu_bwd(gu, K.dgrad(dy_e, ex.lin2.weight), F_)
@@ -141,20 +159,21 @@ def _experts_backward_loop(experts, up, gate, arena, xs, gus, acts, segs, dy, F_
     return dxs
 
 
-def run_experts_forward(owner, arena, experts, up, gate, xs, counts, offsets, max_rows, F_):
+def run_experts_forward(owner, arena, experts, up, gate, xs, counts, offsets, max_rows, F_, activation="swiglu"):
     """All experts on the sorted rows ``xs``, on the path ``SEGMENTED`` (read here, at call time) selects.  Returns (y, gus, acts, segs), what the layers
-    save: ``segs`` None = segmented (gus / acts are the whole sorted buffers), else the per-expert path's segment list."""
+    save: ``segs`` None = segmented (gus / acts are the whole sorted buffers), else the per-expert path's segment list.  ``activation``: "swiglu"
+    (a = u * silu(g)) or "relu2" (a = u * relu(g)^2, unfused, ``csrc/latent_moe.hip``)."""
     if SEGMENTED:  # every product once over all experts, the segment table read on the device: no host read, no per-expert launch
-        gus, acts, y = experts_forward(expert_stacks(owner, arena, experts, up, gate), xs, counts, offsets, max_rows, F_)
+        gus, acts, y = experts_forward(expert_stacks(owner, arena, experts, up, gate), xs, counts, offsets, max_rows, F_, activation)
         return y, gus, acts, None
-    return _experts_forward_loop(experts, up, gate, arena, xs, counts.tolist(), F_)  # the device-to-host read the segmented path does without
+    return _experts_forward_loop(experts, up, gate, arena, xs, counts.tolist(), F_, activation)  # the device-to-host read the segmented path does without
 
 
-def run_experts_backward(owner, arena, experts, up, gate, xs, gus, acts, segs, dy, counts, offsets, max_rows, F_, wg):
+def run_experts_backward(owner, arena, experts, up, gate, xs, gus, acts, segs, dy, counts, offsets, max_rows, F_, wg, activation="swiglu"):
     """d(xs) [R, d] on the path the forward took.  Segmented, the experts' weight gradients go straight into the arena; per expert they are recorded in ``wg``."""
     if segs is None:
-        return experts_backward(expert_stacks(owner, arena, experts, up, gate), arena, xs, gus, acts, dy, counts, offsets, max_rows, F_)
-    return _experts_backward_loop(experts, up, gate, arena, xs, gus, acts, segs, dy, F_, wg)
+        return experts_backward(expert_stacks(owner, arena, experts, up, gate), arena, xs, gus, acts, dy, counts, offsets, max_rows, F_, activation)
+    return _experts_backward_loop(experts, up, gate, arena, xs, gus, acts, segs, dy, F_, wg, activation)
 
 
 # ----------------------------------------------------------------------------------------------- the layer
