@@ -149,6 +149,12 @@ SIGNATURES = {
     "mi355_latmoe_route_bwd": [_L, _I, _I, _P, _P, _P, _P, _L, _F, _P, _L, _P],
     "mi355_latmoe_relu2_glu_fwd": [_L, _I, _P, _L, _P, _L, _P],
     "mi355_latmoe_relu2_glu_bwd": [_L, _I, _P, _L, _P, _L, _P, _L, _P],
+    # Classic MoE: softmax router with the z-loss's logsumexp, the loss, per-expert bias (+ GELU) and bias gradients on the sorted buffer (csrc/classic_moe.hip)
+    "mi355_cmoe_route_fwd": [_L, _I, _I, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P],
+    "mi355_cmoe_route_bwd": [_L, _I, _I, _P, _P, _P, _P, _P, _L, _P, _P, _F, _F, _P, _P, _L, _P],
+    "mi355_cmoe_loss": [_L, _P, _F, _P, _P, _P],
+    "mi355_cmoe_bias_act_fwd": [_L, _I, _I, _P, _P, _P, _L, _P, _L, _P, _L, _P, _L, _I, _P],
+    "mi355_cmoe_segment_colsum": [_L, _I, _I, _P, _P, _P, _L, _P, _I, _P, _L, _I, _I, _P],
     # MiMo-V2-Flash: attention with a sink and its own v head dim, the sink gradient, per-head RMSNorm + partial RoPE (csrc/mimo.hip)
     "mi355_sink_attn_fwd": [_I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _P, _L, _P, _F, _P],
     "mi355_sink_attn_bwd": [_I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P, _L, _P, _L, _P, _I, _F, _P],

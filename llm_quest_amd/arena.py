@@ -80,14 +80,8 @@ class ParamArena:
         off = self.offsets[i]
         return self.grad[off : off + p.numel()].view(p.shape)
 
-    def grad_target(self, first, last=None):
-        """Destination for a wgrad kernel covering parameters first..last: returns (view, accumulate).
-
-        Attaches ``p.grad`` to the arena when it is None (after ``zero_grad(set_to_none=True)``); ``accumulate`` is False
-        only if every covered gradient is stale and may simply be overwritten.
-        """
-        i = self.index(first)
-        j = i if last is None else self.index(last)
+    def _claim(self, i, j):
+        """Attach ``p.grad`` of parameters i..j to the arena, resolve mixed fresh / stale states -> accumulate."""
         states = []
         for t in range(i, j + 1):
             p = self.params[t]
@@ -107,6 +101,17 @@ class ParamArena:
         accumulate = not all(states)
         for t in range(i, j + 1):
             self._fresh[t] = False
+        return accumulate
+
+    def grad_target(self, first, last=None):
+        """Destination for a wgrad kernel covering parameters first..last: returns (view, accumulate).
+
+        Attaches ``p.grad`` to the arena when it is None (after ``zero_grad(set_to_none=True)``); ``accumulate`` is False
+        only if every covered gradient is stale and may simply be overwritten.
+        """
+        i = self.index(first)
+        j = i if last is None else self.index(last)
+        accumulate = self._claim(i, j)
         start = self.offsets[i]
         end = self.offsets[j] + self.params[j].numel()
         flat = self.grad[start:end]
@@ -114,6 +119,13 @@ class ParamArena:
             return flat.view(first.shape), accumulate
         k = first.shape[1]
         return flat.view(-1, k), accumulate
+
+    def grad_range(self, first, last):
+        """``grad_target`` for a range of parameters of ANY shapes (weights and biases side by side): returns (flat view, accumulate); the caller
+        addresses the gradients through views of its own."""
+        i, j = self.index(first), self.index(last)
+        accumulate = self._claim(i, j)
+        return self.grad[self.offsets[i] : self.offsets[j] + self.params[j].numel()], accumulate
 
     def untouched_to_zero(self):
         """Parameters whose gradient was not produced this backward get a zero gradient (attached, fresh cleared)."""
