@@ -1,19 +1,12 @@
 """Autograd layer of the DeepSeekMoE path: the layer (``DeepSeekMoE``) and the DeepSeek-V3 block that holds one, as ONE node each.
 
-Same construction as ``ops_moe.py``, which owns the routed experts' part: ``ops_moe.run_experts_forward`` / ``run_experts_backward`` run the products as
-segmented GEMMs (gate-up + SwiGLU, ``lin2``, the two dgrads and the two weight gradients are one launch each over all routed experts, the plan's
-``counts`` / ``offsets`` read on the device), so the layer's forward and backward contain no device-to-host read and their launch count does not grow with
-the number of experts; ``MI355_MOE_SEGMENTED=0`` (``ops_moe.SEGMENTED``) takes the per-expert path there (one host read of the counts, two or three
-launches per expert).  Plan, row dispatch, combine (one kernel; the shared experts' output is its optional addend), combine backward and router backward
-are ``csrc/moe.hip`` (launchers ``kernels_moe.py``); the bias-balanced router, the bias update, the shared experts' bias + SiLU and the fixed-order column
-sums of the bias gradients are ``csrc/deepseek_moe.hip`` (launchers ``kernels_dsmoe.py``).
+What the mixture-of-experts layers share is ``ops_moe.py``'s: the padded gate, the routed core (plan, row dispatch, experts, combine and their backwards),
+the routed experts on segmented GEMMs or, with ``MI355_MOE_SEGMENTED=0`` (``ops_moe.SEGMENTED``), per expert, and the single-output nodes.  This file
+states what is DeepSeekMoE's own: the bias-balanced router and the bias update, the shared experts (their output is the combine's optional addend), their
+bias + SiLU and the fixed-order column sums of the bias gradients (``csrc/deepseek_moe.hip``, launchers ``kernels_dsmoe.py``), and the block.
 
-Two layout points:
-  * a routed expert is lin2(silu(lin1(x)) * lin_gate(x)): the SiLU sits on ``lin1``.  The fused gate-up kernels compute u * silu(g) on [u | g], so
-    the arena holds ``lin_gate`` BEFORE ``lin1`` (``arena_named_params``); the module's parameter names and ``state_dict`` order stay upstream's.
-  * the gate has N = routed experts outputs, any value in 1..128.  When that is no multiple of 8 the gate's three products (forward, dgrad, weight
-    gradient) run on a zero-padded scratch copy of ``gate.weight`` / ``gate.bias`` with ceil8(N) rows, and on logits / dlogits buffers of that
-    pitch whose pad columns the router never reads and the backward leaves zero.
+Layout: a routed expert is lin2(silu(lin1(x)) * lin_gate(x)): the SiLU sits on ``lin1``.  The fused gate-up kernels compute u * silu(g) on [u | g], so
+the arena holds ``lin_gate`` BEFORE ``lin1`` (``arena_named_params``); the module's parameter names and ``state_dict`` order stay upstream's.
 """
 
 import re
@@ -27,9 +20,9 @@ from . import kernels_g3 as KG
 from . import kernels_moe as KM
 from . import ops, ops_mla, ops_moe
 from .arena import ParamArena
-from .ops_g3 import _add_vecgrad, _flat
+from .ops_g3 import _add_vecgrad, _flat, _param_list
 
-BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
+BF16 = torch.bfloat16
 _LIN1 = re.compile(r"(^|\.)routed_experts\.\d+\.lin1\.weight$")
 
 
@@ -51,30 +44,6 @@ def ensure_arena(module):
             if getattr(m, "_arena", None) is None:
                 object.__setattr__(m, "_arena", ar)
     return ops.arena_for(module)
-
-
-# ----------------------------------------------------------------------------------------------- the gate
-def _gate_operands(moe):
-    """(weight [Ep, d] bf16, bias fp32 [Ep]) with Ep = ceil8(routed experts): the parameters themselves, or their zero-padded scratch copies."""
-    E = moe.num_routed
-    Ep = (E + 7) // 8 * 8
-    w, b = moe.gate.weight.detach(), K.cast(moe.gate.bias.detach(), F32)
-    if Ep == E:
-        return w, b
-    wp = torch.zeros((Ep, w.shape[1]), dtype=BF16, device=w.device)
-    bp = torch.zeros((Ep,), dtype=F32, device=w.device)
-    wp[:E].copy_(w)
-    bp[:E].copy_(b)
-    return wp, bp
-
-
-def _forced(moe, T, what="DeepSeekMoE"):
-    f = getattr(moe, "_forced_topk", None)
-    if f is None:
-        return None
-    if tuple(f.shape) != (T, moe.top_k):
-        raise ValueError(f"{what}: the forced selection must be (tokens, top_k) = {(T, moe.top_k)}, got {tuple(f.shape)}")
-    return f.to(dtype=I32).contiguous()
 
 
 # ----------------------------------------------------------------------------------------------- shared experts
@@ -128,115 +97,56 @@ def _flush(wg):
 
 
 # ----------------------------------------------------------------------------------------------- the layer
+def _experts(moe, arena):
+    """[u | g] = [lin_gate | lin1]: a = lin_gate(x) * silu(lin1(x)); segmented or per expert as ops_moe.SEGMENTED says."""
+    return ops_moe.GateUpExperts(moe, arena, moe.routed_experts, "lin_gate", "lin1", moe.routed_experts[0].hidden_dim)
+
+
 def moe_forward(moe, arena, h, residual, keep):
     """h bf16 [T, d] contiguous -> residual + shared(h) + routed(h) [T, d]; updates ``moe.biases`` and sets ``moe.max_vio`` on the device."""
-    E, k, F_ = moe.num_routed, moe.top_k, moe.routed_experts[0].hidden_dim
-    T, d = h.shape
-    wg8, bg8 = _gate_operands(moe)
-    logits = K.gemm(L.GEMM_NT, h, wg8, bias=bg8)  # bf16(h W^T + b): one rounding after the bias is in, as addmm
-    p, idx, w, s = KD.route_fwd(logits[:, :E], moe.biases, k, _forced(moe, T))
-    counts, offsets, slot, row_token, _ = KM.plan(idx, E)
-    max_vio = KD.bias_update(counts, moe.biases, moe.bias_update_rate)  # after this forward's router, on its stream
+    E, T = moe.num_routed, h.shape[0]
+    logits, wg8 = ops_moe.gate_forward(moe.gate, E, h)
+    route = KD.route_fwd(logits[:, :E], moe.biases, moe.top_k, ops_moe._forced(moe, T, "DeepSeekMoE"))
+    sh_out, sh_saved = shared_forward(moe.shared_experts, h, keep) if moe.num_shared > 0 else (None, None)
+    out, _, routed = ops_moe.routed_forward(_experts(moe, arena), h, route, E, residual=residual, shared=sh_out)
+    max_vio = KD.bias_update(routed.counts, moe.biases, moe.bias_update_rate)  # after this forward's router, on its stream
     object.__setattr__(moe, "max_vio", max_vio.reshape(()))
-    object.__setattr__(moe, "_routed", (idx, counts))  # this forward's selection and counts, device tensors (tests and metrics; nothing here reads them back)
-    xs = KM.gather_rows(h, row_token)
-    # [u | g] = [lin_gate | lin1]: a = lin_gate(x) * silu(lin1(x)); segmented or per expert as ops_moe.SEGMENTED says
-    y, gus, acts, segs = ops_moe.run_experts_forward(moe, arena, moe.routed_experts, "lin_gate", "lin1", xs, counts, offsets, T * k, F_)
-    sh_out, sh_saved = (None, None)
-    if moe.num_shared > 0:
-        sh_out, sh_saved = shared_forward(moe.shared_experts, h, keep)
-    out = KM.combine_fwd(y, slot, w, residual, shared=sh_out)
-    saved = (h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, offsets, wg8, sh_saved) if keep else None
-    return out, saved
+    object.__setattr__(moe, "_routed", (routed.idx, routed.counts))  # this forward's selection and counts, device tensors (tests and metrics; nothing here reads them back)
+    return out, ((h, routed, wg8, sh_saved) if keep else None)
 
 
 def moe_backward(moe, arena, saved, dout, wg):
     """d(h) [T, d] of ``moe_forward`` (the residual's share is the caller's)."""
-    h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, offsets, wg8, sh_saved = saved
-    E, F_ = moe.num_routed, moe.routed_experts[0].hidden_dim
-    T = h.shape[0]
-    dy, dw = KM.combine_bwd(dout, row_token, slot, w, y)
-    dxs = ops_moe.run_experts_backward(moe, arena, moe.routed_experts, "lin_gate", "lin1", xs, gus, acts, segs, dy, counts, offsets, T * moe.top_k, F_, wg)
-    dh = KM.combine_fwd(dxs, slot)  # the gather's backward
-    # the gate: dlogits on the padded pitch (pad columns zero), dgrad on the padded weight, the weight gradient through an fp32 scratch
-    Ep = wg8.shape[0]
-    dlog = (torch.zeros if Ep != E else torch.empty)((T, Ep), dtype=BF16, device=h.device)
-    KM.route_bwd(dw, w, s, idx, p, dlogits=dlog[:, :E])
-    K.gemm(L.GEMM_NN, dlog, wg8, out=dh, residual=dh)
-    gate = moe.gate
-    if gate.weight.requires_grad:
-        if Ep == E:
-            ops._wgrad(arena, gate.weight, None, dlog, h, wg)
-        else:
-            g32 = K.gemm(L.GEMM_TN, dlog, h, out_dtype=F32)  # [Ep, d]; rows E.. are zero
-            view, acc = arena.grad_target(gate.weight)
-            K.add_f32_to_bf16(g32[:E].reshape(-1), view if acc else None, view)
-    if gate.bias.requires_grad:
-        _add_vecgrad(arena, gate.bias, KD.colsum(dlog)[:E])
+    h, r, wg8, sh_saved = saved
+    E = moe.num_routed
+    dh, dw = ops_moe.routed_backward(_experts(moe, arena), r, dout, wg)
+    dlog = ops_moe.gate_buffer(h.shape[0], E, h.device)
+    KM.route_bwd(dw, r.w, r.s, r.idx, r.p, dlogits=dlog[:, :E])
+    ops_moe.gate_backward(moe.gate, E, arena, h, wg8, dlog, dh, wg)
     if sh_saved is not None:
         dh = shared_backward(moe.shared_experts, arena, h, sh_saved, dout, wg, dh)
     return dh
 
 
-def _check(module, x, what):
-    ops_mla._check_activation(x, what)
-    ops_mla.check_bf16(module, what)
+def _shared_node_forward(sh, arena, h, keep):
+    out, saved = shared_forward(sh, h, keep)
+    return out, ((h, saved) if keep else None)
 
 
-class DeepSeekMoEFn(torch.autograd.Function):
-    """``DeepSeekMoE.forward`` on [..., d] bf16."""
-
-    @staticmethod
-    def forward(ctx, x, moe, keep, *params):
-        arena = ensure_arena(moe)
-        h = _flat(x)
-        out, saved = moe_forward(moe, arena, h, None, keep)
-        ctx.moe, ctx.saved, ctx.shp = moe, saved, x.shape
-        return out.view(x.shape)
-
-    @staticmethod
-    def backward(ctx, dout):
-        moe, saved = ctx.moe, ctx.saved
-        if saved is None:
-            raise RuntimeError("DeepSeekMoEFn: backward through a forward that ran without grad mode")
-        wg = []
-        dh = moe_backward(moe, ensure_arena(moe), saved, _flat(dout), wg)
-        _flush(wg)
-        ctx.saved = None
-        return (dh.view(ctx.shp), None, None) + (None,) * len(moe._param_list)
+DeepSeekMoEFn = ops_moe.single_output_node(  # ``DeepSeekMoE.forward`` on [..., d] bf16
+    "DeepSeekMoEFn", lambda moe, arena, h, keep: moe_forward(moe, arena, h, None, keep), moe_backward, ensure_arena, _flush)
+SharedExpertsFn = ops_moe.single_output_node(  # ``VectorizedSharedExperts.forward`` called on its own
+    "VectorizedSharedExperts", _shared_node_forward, lambda sh, arena, saved, dout, wg: shared_backward(sh, arena, *saved, dout, wg), ensure_arena, _flush)
 
 
 def run_moe(moe, x):
-    _check(moe, x, "DeepSeekMoE")
-    return DeepSeekMoEFn.apply(x, moe, torch.is_grad_enabled(), *ops_mla._param_list(moe))
-
-
-class SharedExpertsFn(torch.autograd.Function):
-    """``VectorizedSharedExperts.forward`` called on its own."""
-
-    @staticmethod
-    def forward(ctx, x, sh, keep, *params):
-        ensure_arena(sh)
-        h = _flat(x)
-        out, saved = shared_forward(sh, h, keep)
-        ctx.sh, ctx.saved, ctx.shp = sh, ((h, saved) if keep else None), x.shape
-        return out.view(x.shape)
-
-    @staticmethod
-    def backward(ctx, dout):
-        if ctx.saved is None:
-            raise RuntimeError("VectorizedSharedExperts: backward through a forward that ran without grad mode")
-        h, saved = ctx.saved
-        wg = []
-        dh = shared_backward(ctx.sh, ensure_arena(ctx.sh), h, saved, _flat(dout), wg)
-        _flush(wg)
-        ctx.saved = None
-        return (dh.view(ctx.shp), None, None) + (None,) * len(ctx.sh._param_list)
+    ops_moe._check(moe, x, "DeepSeekMoE")
+    return DeepSeekMoEFn.apply(x, moe, torch.is_grad_enabled(), *_param_list(moe))
 
 
 def run_shared(sh, x):
-    _check(sh, x, "VectorizedSharedExperts")
-    return SharedExpertsFn.apply(x, sh, torch.is_grad_enabled(), *ops_mla._param_list(sh))
+    ops_moe._check(sh, x, "VectorizedSharedExperts")
+    return SharedExpertsFn.apply(x, sh, torch.is_grad_enabled(), *_param_list(sh))
 
 
 # ----------------------------------------------------------------------------------------------- the block
@@ -283,5 +193,5 @@ class DeepSeekMoEBlockFn(torch.autograd.Function):
 
 
 def run_block(blk, x, rt):
-    _check(blk, x, "DeepSeek MoE TransformerBlock")
-    return DeepSeekMoEBlockFn.apply(x, blk, rt, torch.is_grad_enabled(), *ops_mla._param_list(blk))
+    ops_moe._check(blk, x, "DeepSeek MoE TransformerBlock")
+    return DeepSeekMoEBlockFn.apply(x, blk, rt, torch.is_grad_enabled(), *_param_list(blk))

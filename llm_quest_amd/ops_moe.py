@@ -13,56 +13,85 @@ reads the ``E`` counts once per forward, then runs two or three launches per exp
 caller's grouped launches.  Per segment both paths compute the same sums (the segmented kernels are bit-identical to the per-expert calls on the
 128x128 tile).
 
-This module owns the experts' part of BOTH mixture-of-experts layers: the stacks, the segmented launches, the per-expert loops and the choice between
-the two paths (``run_experts_forward`` / ``run_experts_backward``) take the expert list and the names of the fused pair's two halves, so ``ops_dsmoe.py``
-(routed experts, ``lin_gate`` before ``lin1``) and the two bench tools call them and restate nothing.
+This module also owns what the four mixture-of-experts layers (this one, ``ops_dsmoe.py``, ``ops_latmoe.py``, ``ops_cmoe.py``) have in common, stated once:
+  * the experts' part of the gate-up layers: the stacks, the segmented launches, the per-expert loops and the choice between the two paths
+    (``run_experts_forward`` / ``run_experts_backward``, which take the expert list and the names of the fused pair's two halves), and ``GateUpExperts``,
+    the adapter the routed core drives them through; ``build_stacks`` and ``_segments`` serve the classic layer's own experts as well;
+  * the routed core: ``routed_forward`` (plan, row dispatch, experts, weighted combine) and ``routed_backward`` (combine backward, experts backward, the
+    gather's backward) around a ``Routed`` record of what the backward needs;
+  * the padded gate: a gate has N = routed experts outputs, any value in 1..128.  When that is no multiple of 8 its three products (forward, dgrad, weight
+    gradient) run on zero-padded scratch copies of ``gate.weight`` / ``gate.bias`` with ceil8(N) rows and on logits / dlogits buffers of that pitch, whose
+    pad columns the routers never read and the backward leaves zero (``gate_operands``, ``gate_forward``, ``gate_buffer``, ``gate_backward``);
+  * ``single_output_node``, the autograd node of a module with one output, and the small helpers ``_forced``, ``_loss_grad``, ``_loss_out``, ``_check``.
 """
 
+import collections
 import os
 
 import torch
 
 from . import _lib as L
 from . import kernels as K
+from . import kernels_dsmoe as KD
 from . import kernels_latmoe as KL
 from . import kernels_moe as KM
 from . import ops
+from .ops_g3 import _add_vecgrad, _check_activation, _flat, check_bf16
 
-BF16, F32 = torch.bfloat16, torch.float32
+BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 SEGMENTED = os.environ.get("MI355_MOE_SEGMENTED", "1") != "0"  # 0: one launch per expert and product, behind a host read of the counts (A/B measurements, the tests' comparison)
 
 
 # ----------------------------------------------------------------------------------------------- the experts as stacks
 class ExpertStacks:
-    """The experts' weights and gradients as 3-D stacks [E, rows, cols] over the arena (``K.expert_stack``): ``wgu`` [E, 2F, d] the fused gate-up pair,
-    ``w2`` [E, d, F], ``ggu`` / ``g2`` the same views of the gradient arena; ``first`` / ``last`` = the parameter range ``arena.grad_target`` covers."""
-
-    __slots__ = ("ptrs", "wgu", "w2", "ggu", "g2", "first", "last", "params")
+    """The experts' parameters and gradients as 3-D stacks [E, rows, cols] over the arena (``K.expert_stack``), one attribute per name ``build_stacks`` is
+    given; ``first`` / ``last`` = the parameter range ``arena.grad_target`` covers, ``params`` that range, ``ptrs`` the arena state the views belong to."""
 
 
-def expert_stacks(owner, arena, experts, up, gate):
-    """``owner``'s stacks, rebuilt when the arena moved.  ``up`` / ``gate`` name the two halves of the fused pair in the arena's order.  Raises unless every
-    expert's three parameters are consecutive in the arena and the experts follow each other at one stride."""
+def build_stacks(owner, arena, experts, what, names, describe):
+    """``owner``'s stacks, cached on it and rebuilt when the arena moved.  ``describe(ex)`` -> (the expert's parameters in the arena's order, one tensor per
+    stack); ``names``: (stack, gradient stack) per tensor, the gradient stack being the same view of the gradient arena.  Raises unless every expert's
+    parameters are consecutive in the arena and the experts follow each other at one stride."""
     st = getattr(owner, "_expert_stacks", None)
     if st is not None and st.ptrs is arena._ptrs:
         return st
-    pairs = [(getattr(ex, up).weight, getattr(ex, gate).weight) for ex in experts]
+    params, tensors = zip(*(describe(ex) for ex in experts))
     st = ExpertStacks()
-    st.wgu = K.expert_stack([arena.fused(a, b) for a, b in pairs])
-    st.w2 = K.expert_stack([ex.lin2.weight.detach() for ex in experts])
-    st.first, st.last = pairs[0][0], experts[-1].lin2.weight
+    for (name, _), per_expert in zip(names, zip(*tensors)):
+        setattr(st, name, K.expert_stack(list(per_expert)))
+    st.first, st.last = params[0][0], params[-1][-1]
     i, j = arena.index(st.first), arena.index(st.last)
-    if j - i + 1 != 3 * len(experts) or arena.data.storage_offset() != 0 or arena.grad.storage_offset() != 0:
-        raise RuntimeError("segmented MoE: the experts' parameters are not one consecutive range of the arena")
+    if j - i + 1 != len(params[0]) * len(experts) or arena.data.storage_offset() != 0 or arena.grad.storage_offset() != 0:
+        raise RuntimeError(f"{what}: the experts' parameters are not one consecutive range of the arena")
     st.params = arena.params[i : j + 1]
-    st.ggu = arena.grad.as_strided(st.wgu.size(), st.wgu.stride(), st.wgu.storage_offset())
-    st.g2 = arena.grad.as_strided(st.w2.size(), st.w2.stride(), st.w2.storage_offset())
+    for name, grad in names:
+        v = getattr(st, name)
+        setattr(st, grad, arena.grad.as_strided(v.size(), v.stride(), v.storage_offset()))
     st.ptrs = arena._ptrs
     object.__setattr__(owner, "_expert_stacks", st)
     return st
 
 
-def _check_activation(activation):
+def expert_stacks(owner, arena, experts, up, gate):
+    """The gate-up experts' stacks: ``wgu`` [E, 2F, d] the fused pair, ``w2`` [E, d, F], ``ggu`` / ``g2`` their gradients.  ``up`` / ``gate`` name the two
+    halves of the fused pair in the arena's order."""
+    def describe(ex):
+        u, g, w2 = getattr(ex, up).weight, getattr(ex, gate).weight, ex.lin2.weight
+        return (u, g, w2), (arena.fused(u, g), w2.detach())
+
+    return build_stacks(owner, arena, experts, "segmented MoE", (("wgu", "ggu"), ("w2", "g2")), describe)
+
+
+def _segments(n_rows):
+    """The per-expert path's (offset, rows) list from the counts as a host list: every start rounded up to the plan's alignment."""
+    align, segs, off = KM.row_align(), [], 0
+    for n in n_rows:
+        segs.append((off, n))
+        off += (n + align - 1) // align * align
+    return segs
+
+
+def _is_relu2(activation):
     if activation not in ("swiglu", "relu2"):
         raise ValueError(f"moe: the experts' activation must be 'swiglu' or 'relu2', got {activation!r}")
     return activation == "relu2"
@@ -72,7 +101,7 @@ def experts_forward(st, xs, counts, offsets, max_rows, F_, activation="swiglu"):
     """(gu [R, 2F], a [R, F], y [R, d]) of all experts on the sorted rows ``xs``: two launches (three when F % 32 != 0 keeps the unfused SwiGLU kernel, which
     then runs once over the whole sorted buffer; padding rows hold no defined value and are never read through slot / row_token).  ``activation``
     "relu2" (LatentMoE: a = u * relu(g)^2) always takes that unfused route, with ``KL.relu2_glu_fwd`` as the activation kernel."""
-    if _check_activation(activation):
+    if _is_relu2(activation):
         gu = K.gemm_segmented(L.GEMM_NT, xs, st.wgu, counts, offsets, max_rows)
         a = KL.relu2_glu_fwd(gu, F_)
     elif ops.FUSE_SWIGLU_FWD and F_ % 32 == 0:
@@ -88,7 +117,7 @@ def experts_backward(st, arena, xs, gu, a, dy, counts, offsets, max_rows, F_, ac
     """d(xs) [R, d]; the experts' weight gradients go straight into the arena: two dgrad launches (+ the unfused SwiGLU backward when switched off, or the
     squared-ReLU backward for ``activation`` "relu2") and two weight-gradient launches over all experts.  An expert without a token ends with an exactly
     zero (or, accumulating, unchanged) attached gradient."""
-    if _check_activation(activation):
+    if _is_relu2(activation):
         dgu = KL.relu2_glu_bwd(gu, K.gemm_segmented(L.GEMM_NN, dy, st.w2, counts, offsets, max_rows), F_)
     elif ops.FUSE_SWIGLU_BWD:
         dgu = K.gemm_segmented(L.GEMM_NN, dy, st.w2, counts, offsets, max_rows, epilogue="swiglu_bwd", second=gu)
@@ -109,13 +138,11 @@ def experts_backward(st, arena, xs, gu, a, dy, counts, offsets, max_rows, F_, ac
 def _experts_forward_loop(experts, up, gate, arena, xs, n_rows, F_, activation="swiglu"):
     """The per-expert path (``SEGMENTED`` off): two or three launches per expert that received tokens.  ``n_rows``: the counts as a host list (the layer's
     device-to-host read); ``experts, up, gate`` as for ``expert_stacks``.  Returns (y, gus, acts, segs)."""
-    align = KM.row_align()
     y = torch.empty_like(xs)  # rows no expert writes (padding) are never read: the combine kernels go through slot / row_token
-    relu2 = _check_activation(activation)
+    relu2 = _is_relu2(activation)
     fused = ops.FUSE_SWIGLU_FWD and F_ % 32 == 0 and not relu2
-    segs, gus, acts, off = [], [], [], 0
-    for ex, n in zip(experts, n_rows):
-        segs.append((off, n))
+    segs, gus, acts = _segments(n_rows), [], []
+    for ex, (off, n) in zip(experts, segs):
         if n == 0:
             gus.append(None)
             acts.append(None)
@@ -129,13 +156,12 @@ def _experts_forward_loop(experts, up, gate, arena, xs, n_rows, F_, activation="
         K.gemm(L.GEMM_NT, a, ex.lin2.weight, out=y[off : off + n])
         gus.append(gu)
         acts.append(a)
-        off += (n + align - 1) // align * align
     return y, gus, acts, segs
 
 
 def _experts_backward_loop(experts, up, gate, arena, xs, gus, acts, segs, dy, F_, wg, activation="swiglu"):
     """The per-expert path's d(xs): the forward's segment lengths again, the weight gradients recorded in ``wg`` for the caller's grouped launches."""
-    relu2 = _check_activation(activation)
+    relu2 = _is_relu2(activation)
     dxs = torch.empty_like(xs)  # as y: only the rows in use are read back
     for ex, (off, n), gu, a in zip(experts, segs, gus, acts):
         first, last = getattr(ex, up).weight, getattr(ex, gate).weight
@@ -176,13 +202,151 @@ def run_experts_backward(owner, arena, experts, up, gate, xs, gus, acts, segs, d
     return _experts_backward_loop(experts, up, gate, arena, xs, gus, acts, segs, dy, F_, wg, activation)
 
 
-# ----------------------------------------------------------------------------------------------- the layer
+class GateUpExperts:
+    """The routed experts of a gate-up layer as the routed core takes them: ``run_experts_forward`` / ``run_experts_backward`` (this module's, looked up
+    at call time) on ``experts`` with the fused pair [``up`` | ``gate``].  The default activation is not restated in the calls."""
+
+    def __init__(self, owner, arena, experts, up, gate, F_, activation="swiglu"):
+        self.args, self.F_ = (owner, arena, experts, up, gate), F_
+        self.kw = {} if activation == "swiglu" else {"activation": activation}
+
+    def forward(self, xs, counts, offsets, max_rows):
+        y, gus, acts, segs = run_experts_forward(*self.args, xs, counts, offsets, max_rows, self.F_, **self.kw)
+        return y, (gus, acts), segs
+
+    def backward(self, r, dy, max_rows, wg):
+        return run_experts_backward(*self.args, r.xs, *r.expert_ctx, r.segs, dy, r.counts, r.offsets, max_rows, self.F_, wg, **self.kw)
+
+
+# ----------------------------------------------------------------------------------------------- the routed core
+# What ``routed_backward`` and a router's backward need of one ``routed_forward``: the sorted rows ``xs`` and the experts' output ``y`` on them, the experts'
+# own saved tensors, ``segs`` (None = segmented, else the per-expert path's segment list), the plan and the router's (w, s, idx, p).
+Routed = collections.namedtuple("Routed", "xs y expert_ctx segs slot row_token w s idx p counts offsets")
+
+
+def routed_forward(experts, rows, route, E, psum=None, load_coeff=0.0, residual=None, shared=None):
+    """Plan, row dispatch, experts, weighted combine: residual + (shared + sum_j w[t, j] experts(rows)[slot[t, j]]).  ``route``: the router's
+    (p, idx, w, s); ``experts``: an object with forward(xs, counts, offsets, max_rows) -> (y, its saved tensors, segs) and backward(routed, dy, max_rows, wg)
+    -> d(xs).  With ``psum`` the plan also returns the load loss.  Returns (out, load loss fp32 [1] or None, ``Routed``)."""
+    p, idx, w, s = route
+    counts, offsets, slot, row_token, loss = KM.plan(idx, E, psum, load_coeff)
+    xs = KM.gather_rows(rows, row_token)
+    y, expert_ctx, segs = experts.forward(xs, counts, offsets, idx.numel())
+    out = KM.combine_fwd(y, slot, w, residual, shared=shared)
+    return out, loss, Routed(xs, y, expert_ctx, segs, slot, row_token, w, s, idx, p, counts, offsets)
+
+
+def routed_backward(experts, r, dout, wg, with_dw=True):
+    """(d(rows) [T, width], dw fp32 [T, k] for the router's backward, None without ``with_dw``) of ``routed_forward``; the residual's and the shared addend's
+    shares are the caller's.  The experts' weight gradients go into the arena or are recorded in ``wg``."""
+    dy, dw = KM.combine_bwd(dout, r.row_token, r.slot, r.w, r.y if with_dw else None)
+    dxs = experts.backward(r, dy, r.idx.numel(), wg)
+    return KM.combine_fwd(dxs, r.slot), dw  # the gather's backward: d(rows)[t] = sum_j dxs[slot[t, j]]
+
+
+# ----------------------------------------------------------------------------------------------- the padded gate
+def _ceil8(E):
+    return (E + 7) // 8 * 8
+
+
+def gate_operands(gate, E):
+    """(weight [Ep, d] bf16, bias fp32 [Ep] or None for a gate without one) with Ep = ceil8(E routed experts): the parameters themselves, or their
+    zero-padded scratch copies."""
+    w = gate.weight.detach()
+    b = None if gate.bias is None else K.cast(gate.bias.detach(), F32)
+    Ep = _ceil8(E)
+    if Ep == E:
+        return w, b
+    wp = torch.zeros((Ep, w.shape[1]), dtype=BF16, device=w.device)
+    wp[:E].copy_(w)
+    if b is not None:
+        bp = torch.zeros((Ep,), dtype=F32, device=w.device)
+        bp[:E].copy_(b)
+        b = bp
+    return wp, b
+
+
+def gate_forward(gate, E, h):
+    """(logits [T, Ep] = bf16(h W^T + b), one rounding after the bias is in, as addmm; the weight they were computed with, for ``gate_backward``)."""
+    w8, b8 = gate_operands(gate, E)
+    return K.gemm(L.GEMM_NT, h, w8, bias=b8), w8
+
+
+def gate_buffer(T, E, device):
+    """bf16 [T, Ep] for a router to write its [:, :E] columns of (dlogits, probabilities): pad columns zero, so products and column sums run on the pitch."""
+    Ep = _ceil8(E)
+    return (torch.zeros if Ep != E else torch.empty)((T, Ep), dtype=BF16, device=device)
+
+
+def gate_backward(gate, E, arena, h, w8, dlog, dh, wg):
+    """The gate's backward from ``dlog`` [T, Ep] (a ``gate_buffer``): dh += dlog W on the padded weight, the weight gradient (recorded in ``wg``, or with a
+    padded gate through an fp32 scratch) and, for a gate with a bias, the bias gradient as a fixed-order column sum."""
+    K.gemm(L.GEMM_NN, dlog, w8, out=dh, residual=dh)
+    if gate.weight.requires_grad:
+        if w8.shape[0] == E:
+            ops._wgrad(arena, gate.weight, None, dlog, h, wg)
+        else:
+            g32 = K.gemm(L.GEMM_TN, dlog, h, out_dtype=F32)  # [Ep, d]; rows E.. are zero
+            view, acc = arena.grad_target(gate.weight)
+            K.add_f32_to_bf16(g32[:E].reshape(-1), view if acc else None, view)
+    if gate.bias is not None and gate.bias.requires_grad:
+        _add_vecgrad(arena, gate.bias, KD.colsum(dlog)[:E])  # fixed order: per-row-part partials, then reduce_rows
+
+
+# ----------------------------------------------------------------------------------------------- small helpers of the four layers
+def _forced(moe, T, what):
+    """The selection a test or a replay forces on the router (``moe._forced_topk``) as int32 [T, top_k], or None."""
+    f = getattr(moe, "_forced_topk", None)
+    if f is None:
+        return None
+    if tuple(f.shape) != (T, moe.top_k):
+        raise ValueError(f"{what}: the forced selection must be (tokens, top_k) = {(T, moe.top_k)}, got {tuple(f.shape)}")
+    return f.to(dtype=I32).contiguous()
+
+
+def _loss_grad(g):
+    """The incoming gradient of a layer's loss (0-dim, the activations' dtype) as the fp32 device scalar the route backward reads."""
+    return None if g is None else K.cast(g.reshape(1).contiguous(), F32)
+
+
+def _loss_out(loss, dtype):
+    return None if loss is None else K.cast(loss, dtype).reshape(())
+
+
+def _check(module, x, what):
+    _check_activation(x, what)
+    check_bf16(module, what)
+
+
+def single_output_node(what, forward, backward, arena_of, flush):
+    """The autograd node of a module called on [..., d] bf16 with one output: ``forward(module, arena, h, keep)`` -> (out [T, d], saved or None) and
+    ``backward(module, arena, saved, dout, wg)`` -> d(h) on the flattened tokens; ``flush(wg)`` runs the recorded weight gradients."""
+
+    def node_forward(ctx, x, module, keep, *params):
+        out, saved = forward(module, arena_of(module), _flat(x), keep)
+        ctx.module, ctx.saved, ctx.shp = module, saved, x.shape
+        return out.view(x.shape)
+
+    def node_backward(ctx, dout):
+        if ctx.saved is None:
+            raise RuntimeError(f"{what}: backward through a forward that ran without grad mode")
+        wg = []
+        dh = backward(ctx.module, arena_of(ctx.module), ctx.saved, _flat(dout), wg)
+        flush(wg)
+        ctx.saved = None
+        return (dh.view(ctx.shp), None, None) + (None,) * len(ctx.module._param_list)
+
+    name = what if what.endswith("Fn") else what + "Fn"  # autograd names the backward node after the class
+    return type(name, (torch.autograd.Function,), dict(forward=staticmethod(node_forward), backward=staticmethod(node_backward), __module__=forward.__module__))
+
+
+# ----------------------------------------------------------------------------------------------- the Qwen3 layer
 def _gate_input(moe, h, gate_probas):
     """The router's input: the gate's logits [T, E] (a column slice of a buffer whose pitch is a multiple of 8), or the replayed probabilities
     (qwen3_moe.py:115-118: cast to the activations' dtype, a constant)."""
     T, E = h.shape[0], moe.num_experts
     if gate_probas is None:
-        buf = torch.empty((T, (E + 7) // 8 * 8), dtype=BF16, device=h.device)
+        buf = torch.empty((T, _ceil8(E)), dtype=BF16, device=h.device)
         return K.gemm(L.GEMM_NT, h, moe.gate.weight, out=buf[:, :E]), False
     if gate_probas.dim() != 2:
         raise ValueError("gate_probas must be 2D shaped as (batch*seq, num_experts)")
@@ -195,43 +359,29 @@ def _gate_input(moe, h, gate_probas):
     return K.cast(gp.contiguous(), BF16), True
 
 
+def _experts(moe, arena):
+    return GateUpExperts(moe, arena, moe.experts, "lin1", "lin_gate", moe.experts[0].hidden_dim)
+
+
 def moe_forward(moe, arena, h, residual, gate_probas, keep):
     """h bf16 [T, d] contiguous -> (residual + moe(h) [T, d], load loss fp32 [1] or None, the probabilities routed by, saved or None)."""
-    E, k, F_ = moe.num_experts, moe.top_k, moe.experts[0].hidden_dim
-    T, d = h.shape
     gate_in, replay = _gate_input(moe, h, gate_probas)
-    p, idx, w, s = KM.route_fwd(gate_in, k, replay)
-    psum = K.colsum(p) if moe.training else None
-    counts, offsets, slot, row_token, loss = KM.plan(idx, E, psum, moe.load_coeff)
-    xs = KM.gather_rows(h, row_token)
-    y, gus, acts, segs = run_experts_forward(moe, arena, moe.experts, "lin1", "lin_gate", xs, counts, offsets, T * k, F_)
-    out = KM.combine_fwd(y, slot, w, residual)
-    saved = (h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, offsets, replay) if keep else None
-    return out, loss, p, saved
+    route = KM.route_fwd(gate_in, moe.top_k, replay)
+    psum = K.colsum(route[0]) if moe.training else None
+    out, loss, routed = routed_forward(_experts(moe, arena), h, route, moe.num_experts, psum, moe.load_coeff, residual)
+    return out, loss, route[0], ((h, routed, replay) if keep else None)
 
 
 def moe_backward(moe, arena, saved, dout, g_loss, wg):
     """d(h) [T, d] of ``moe_forward`` (the residual's share is the caller's).  ``g_loss``: dL/d(load loss), fp32 [1] on the device, or None.
     The gate's weight gradient (and, on the per-expert path, the experts') is recorded in ``wg`` for the caller's grouped launches."""
-    h, xs, y, gus, acts, segs, slot, row_token, w, s, idx, p, counts, offsets, replay = saved
-    F_ = moe.experts[0].hidden_dim
-    dy, dw = KM.combine_bwd(dout, row_token, slot, w, None if replay else y)
-    dxs = run_experts_backward(moe, arena, moe.experts, "lin1", "lin_gate", xs, gus, acts, segs, dy, counts, offsets, h.shape[0] * moe.top_k, F_, wg)
-    dh = KM.combine_fwd(dxs, slot)  # the gather's backward: dh[t] = sum_j dxs[slot[t, j]]
+    h, r, replay = saved
+    dh, dw = routed_backward(_experts(moe, arena), r, dout, wg, with_dw=not replay)
     if not replay:  # a replayed routing is a constant: the gate is not evaluated and gets no gradient
-        dlogits = KM.route_bwd(dw, w, s, idx, p, counts, g_loss, moe.load_coeff)
+        dlogits = KM.route_bwd(dw, r.w, r.s, r.idx, r.p, r.counts, g_loss, moe.load_coeff)
         K.gemm(L.GEMM_NN, dlogits, moe.gate.weight, out=dh, residual=dh)
         ops._wgrad(arena, moe.gate.weight, None, dlogits, h, wg)
     return dh
-
-
-def _loss_grad(g):
-    """The incoming gradient of the load loss (0-dim, the activations' dtype) as the fp32 device scalar the route backward reads."""
-    return None if g is None else K.cast(g.reshape(1).contiguous(), F32)
-
-
-def _loss_out(loss, dtype):
-    return None if loss is None else K.cast(loss, dtype).reshape(())
 
 
 class MoEFn(torch.autograd.Function):

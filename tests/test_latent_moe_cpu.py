@@ -201,7 +201,7 @@ def test_host_side_validation_of_the_new_entry_points():
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         SquaredReLU()(torch.zeros(4, 16, dtype=BF16))
     with pytest.raises(ValueError, match="'swiglu' or 'relu2'"):
-        ops_moe._check_activation("gelu")
+        ops_moe._is_relu2("gelu")
     assert all(inspect.signature(f).parameters["activation"].default == "swiglu" for f in (
         ops_moe.run_experts_forward, ops_moe.run_experts_backward, ops_moe.experts_forward, ops_moe.experts_backward, ops_moe._experts_forward_loop,
         ops_moe._experts_backward_loop))

@@ -5,6 +5,10 @@ BOTH paths (the per-expert path stays covered now that the default moved).
 Tolerance: the project's 1.5x rule (``judge`` of test_moe_gpu.py).  Counts and sentinels are compared exactly.
 """
 
+import collections
+import json
+import os
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -147,30 +151,46 @@ def test_forward_and_backward_never_synchronise_with_the_host(switch):
 
 
 # ----------------------------------------------------------------------------------------------------------------- launch count
-def _count_calls(monkeypatch, E):
+def _counted(step):
+    """The entry-point name of every ``L.call`` that ``step()`` makes, in order.  ``L.call`` is put back whether ``step`` returns or raises."""
     from llm_quest_amd import _lib as L
-    from llm_quest_amd.moe.qwen3_moe import Qwen3MoE
 
-    torch.manual_seed(20 + E)
-    moe = Qwen3MoE(dict(emb_dim=64, moe_hidden_dim=64, num_experts=E, top_k=2, aux_loss_coef=0.01, dtype=BF16)).cuda().train()
-    x = torch.randn(1, 70, 64, generator=torch.Generator().manual_seed(21)).to(BF16).cuda().requires_grad_(True)
     names, real = [], L.call
 
     def counting(name, *args):
         names.append(name)
         return real(name, *args)
 
-    monkeypatch.setattr(L, "call", counting)
-    out = moe(x)
-    torch.autograd.backward([out, moe.moe_loss], [torch.ones_like(out), torch.ones((), dtype=BF16, device="cuda")])
-    monkeypatch.setattr(L, "call", real)
-    assert all(p.grad is not None for p in moe.parameters())
+    L.call = counting
+    try:
+        step()
+    finally:
+        L.call = real
     return names
 
 
-def test_launch_count_does_not_depend_on_the_number_of_experts(monkeypatch, switch):
+def _qwen_launch_step(E):
+    from llm_quest_amd.moe.qwen3_moe import Qwen3MoE
+
+    torch.manual_seed(20 + E)
+    moe = Qwen3MoE(dict(emb_dim=64, moe_hidden_dim=64, num_experts=E, top_k=2, aux_loss_coef=0.01, dtype=BF16)).cuda().train()
+    x = torch.randn(1, 70, 64, generator=torch.Generator().manual_seed(21)).to(BF16).cuda().requires_grad_(True)
+
+    def step():
+        out = moe(x)
+        torch.autograd.backward([out, moe.moe_loss], [torch.ones_like(out), torch.ones((), dtype=BF16, device="cuda")])
+        assert all(p.grad is not None for p in moe.parameters())
+
+    return step
+
+
+def _count_calls(E):
+    return _counted(_qwen_launch_step(E))
+
+
+def test_launch_count_does_not_depend_on_the_number_of_experts(switch):
     switch(True)
-    n8, n16 = _count_calls(monkeypatch, 8), _count_calls(monkeypatch, 16)
+    n8, n16 = _count_calls(8), _count_calls(16)
     print(f"  {len(n8)} calls at E = 8, {len(n16)} at E = 16: {sorted(set(n8))}")
     assert n8 == n16
     for names in (n8, n16):
@@ -178,8 +198,66 @@ def test_launch_count_does_not_depend_on_the_number_of_experts(monkeypatch, swit
         assert names.count("mi355_gemm_bf16_segmented") == 4 and names.count("mi355_gemm_bf16_segmented_tn") == 2
         assert names.count("mi355_gemm_bf16_grouped") == 1  # the gate's weight gradient
     switch(False)
-    off8, off16 = _count_calls(monkeypatch, 8), _count_calls(monkeypatch, 16)
+    off8, off16 = _count_calls(8), _count_calls(16)
     assert len(off16) > len(off8) > len(n8) and "mi355_gemm_bf16_segmented" not in off8
+
+
+# ----------------------------------------------------------------------------------------------------------------- the recorded launches
+LAUNCH_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "moe_launches.json")  # written by tools/record_moe_launches.py
+PATHS = {"segmented": True, "per-expert": False}
+
+
+def _latent_launch_step(name):
+    import latent_moe_oracle as LO
+    import test_latent_moe_gpu as TL
+
+    t = LO.load_fixture("latent_moe_tiny")
+    m = TL._layer(name, t)
+    return lambda: TL._step(m, t[name + ".in.x"])
+
+
+def _classic_launch_step(name):
+    import classic_moe_oracle as CO
+    import test_classic_moe_gpu as TC
+
+    t, pre = CO.load_fixture("classic_moe_tiny"), name + "."
+    m = TC._layer(name, t)
+    return lambda: TC._step(m, t[pre + "in.x"], t[pre + "in.dout"], float(t[pre + "in.g"]))
+
+
+# one forward + backward (the loss included where the layer has one) of every mixture-of-experts layer on the fixtures' own tiny shapes: T = 70 tokens,
+# widths 64 to 80; a padded (E = 12, 3, 7) and an unpadded (E = 16, 8, 8) gate, fp32 (LatentMoE A) and bf16 balancing biases
+LAUNCH_CASES = {
+    "LatentMoE A": lambda: _latent_launch_step("A"),
+    "LatentMoE B": lambda: _latent_launch_step("B"),
+    "classic MoE A": lambda: _classic_launch_step("A"),
+    "classic MoE B": lambda: _classic_launch_step("B"),
+    "DeepSeekMoE 7 routed + 1 shared, k 3, T 70": lambda: _deepseek_layer(),
+    "Qwen3MoE E 8": lambda: _qwen_launch_step(8),
+}
+
+
+def launch_counts(case, segmented):
+    """{entry point: number of calls} of the first forward + backward of a freshly built layer, with ``ops_moe.SEGMENTED`` set to ``segmented``."""
+    from llm_quest_amd import ops_moe
+
+    before = ops_moe.SEGMENTED
+    ops_moe.SEGMENTED = bool(segmented)
+    try:
+        return dict(sorted(collections.Counter(_counted(LAUNCH_CASES[case]())).items()))
+    finally:
+        ops_moe.SEGMENTED = before
+
+
+@pytest.mark.parametrize("path", list(PATHS))
+@pytest.mark.parametrize("case", list(LAUNCH_CASES))
+def test_every_layer_issues_the_recorded_launches(case, path):
+    """The host layer may be reorganised, the launches may not change: per entry point, as many calls as tests/golden/moe_launches.json records."""
+    with open(LAUNCH_GOLDEN) as f:
+        want = json.load(f)[case][path]
+    got = launch_counts(case, PATHS[path])
+    print(f"  {case}, {path}: {sum(got.values())} calls")
+    assert got == want, {n: (got.get(n, 0), want.get(n, 0)) for n in sorted(set(got) | set(want)) if got.get(n, 0) != want.get(n, 0)}
 
 
 # ----------------------------------------------------------------------------------------------------------------- layers, both paths

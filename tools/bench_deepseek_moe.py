@@ -78,7 +78,7 @@ def measure_layer(cfg, T, steps, warmup):
                 segmented_ms_median=by_switch[True]["ms_median"], segmented_ms_min=by_switch[True]["ms_min"], segmented_ms_max=by_switch[True]["ms_max"],
                 per_expert_ms_median=by_switch[False]["ms_median"], per_expert_ms_min=by_switch[False]["ms_min"], per_expert_ms_max=by_switch[False]["ms_max"],
                 per_expert_over_segmented=by_switch[False]["ms_median"] / by_switch[True]["ms_median"], **by_switch[default])]
-    wg8, bg8 = ops_dsmoe._gate_operands(moe)
+    wg8, bg8 = ops_moe.gate_operands(moe.gate, E)
     logits = K.gemm(L.GEMM_NT, h, wg8, bias=bg8)
     p, idx, w, s = KD.route_fwd(logits[:, :E], moe.biases, k)
     counts, offsets, slot, row_token, _ = KM.plan(idx, E)
@@ -88,7 +88,7 @@ def measure_layer(cfg, T, steps, warmup):
     scratch = moe.biases.clone()
 
     def router():
-        a, b = ops_dsmoe._gate_operands(moe)
+        a, b = ops_moe.gate_operands(moe.gate, E)
         lg = K.gemm(L.GEMM_NT, h, a, bias=b)
         KD.route_fwd(lg[:, :E], moe.biases, k)
         KD.bias_update(counts, scratch, moe.bias_update_rate)
