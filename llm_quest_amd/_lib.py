@@ -160,6 +160,12 @@ SIGNATURES = {
     "mi355_sink_attn_bwd": [_I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P, _L, _P, _L, _P, _I, _F, _P],
     "mi355_mimo_normrope_fwd": [_L, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _L, _P, _L, _F, _P],
     "mi355_mimo_normrope_bwd": [_L, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _L, _P, _L, _P, _L, _P, _I, _F, _P],
+    # GRPO policy losses: label log-probs over the logits, the per-token loss chain, the one-pass logits loss (csrc/grpo.hip)
+    "mi355_label_logprob_fwd": [_L, _L, _L, _P, _L, _L, _P, _P, _P, _P],
+    "mi355_label_logprob_bwd": [_L, _L, _L, _P, _P, _L, _L, _P, _P, _P, _L, _L, _P],
+    "mi355_grpo_token_loss": [_I, _L, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "mi355_grpo_piece": [_I, _I, _L, _P, _P, _P, _P, _P, _I, _F, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P],
+    "mi355_grpo_logits_loss": [_I, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _P, _P, _P, _I, _F, _F, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
 }
 # size / constant queries: no stream argument, the return value is the answer (name -> (argtypes, restype))
 QUERIES = {

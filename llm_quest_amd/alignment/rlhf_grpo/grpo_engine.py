@@ -1,0 +1,187 @@
+"""The GRPO loss layer (reference: llm_quest/alignment/rlhf_grpo/grpo_engine.py) on the HIP kernels of csrc/grpo.hip.
+
+The functions carry the reference's names, parameter order and defaults, so a training loop written against it (:1082-1111) runs unchanged:
+``log_probs_per_token`` -> the ratio -> ``kl_div_per_token`` -> ``GRPOLoss.compute`` -> ``backward()``.  ``grpo_policy_loss`` is this project's own
+entry for those lines: one call from the logits to the scalar loss, in ONE pass over the logits where the mathematics allows it.
+
+What differs from the reference, on purpose:
+
+* Logits are bf16 device tensors and every log-prob is computed and returned in fp32.  The reference takes ``log_softmax`` in the logits' own dtype
+  (bf16 there), a loss of precision that is not reproduced; ``log_probs_per_token_optimized`` is the same kernel, so its bf16 caveat does not apply.
+* The per-token functions take and return fp32 ``[B, T]`` device tensors; host tensors are refused (there is no CPU fallback), except in ``z_scores``
+  and ``bt_loss``, which work on ``B`` numbers in plain torch on either device.
+* ``loss_mask`` may be bool, an integer type or a float type holding 0 or 1.
+
+Like the reference: a sequence whose mask is empty contributes 0 in the token-level variants; an empty mask gives NaN in ``log_probs_per_seq`` and so
+in GSPO.
+
+Out of scope (not built here): sampling and generation inside the loop, the reward model and ``PrefRewardCalculator``, the collators,
+``rlhf_grpo_training_loop``, the experimental loop and ``GRPOEvaluator``, DPO / RLVR / RPT (their log-prob needs are one call to
+``log_probs_per_token`` away), and fusing the LM-head GEMM into the log-prob pass (vocabulary-chunked, no logits in memory).
+"""
+
+import torch
+import torch.nn.functional as F
+
+from llm_quest_amd import _lib as L
+from llm_quest_amd import config
+from llm_quest_amd import kernels_grpo as K
+from llm_quest_amd import ops_grpo as O
+
+_TOKEN_LEVEL = ("grpo", "dapo", "dr_grpo", "sapo")
+
+
+def bt_loss(chosen_logits, rejected_logits, beta=1.0):
+    """Bradley-Terry loss of the reward model: mean over the batch of -log sigmoid(beta (chosen - rejected)).  ``B`` numbers: plain torch."""
+    return -F.logsigmoid(beta * (chosen_logits - rejected_logits)).mean()
+
+
+def z_scores(rewards, num_samples, dr_grpo=None):
+    """Advantages by outcome supervision: the rewards (B,) standardised inside each group of ``num_samples``; with ``dr_grpo == "dr_grpo"`` only
+    centred.  ``config.use_phantom_reward`` adds one reward of 0 to every group before its statistics.  ``B`` numbers: plain torch."""
+    rewards = rewards.view(-1, num_samples)
+    if config.use_phantom_reward:
+        augmented = torch.cat([rewards, torch.zeros(rewards.shape[0], 1, device=rewards.device)], dim=1)
+    else:
+        augmented = rewards
+    mean = augmented.mean(dim=1, keepdim=True)
+    if dr_grpo == "dr_grpo":
+        return (rewards - mean).view(-1)
+    if not config.use_phantom_reward:
+        assert num_samples > 1, "num_samples must be greater than 1 to get a relative comparison"
+    std = augmented.std(dim=1, keepdim=True)
+    return ((rewards - mean) / (std + 1e-8)).view(-1)
+
+
+def _device_only(*tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("llm_quest_amd GRPO functions run only on an MI355X (HIP) device; got a CPU tensor.  There is no CPU fallback for this path.")
+
+
+def _vector_logits(logits):
+    """The logits as the kernels can address them: as they are, or -- a row pitch that is no multiple of 8 elements -- through the padded copy cross
+    entropy uses (its backward copies the gradient back)."""
+    if K.rows_are_vector_ready(logits):
+        return logits
+    from llm_quest_amd.engine import _pad_rows
+
+    B, S, V = logits.shape
+    return _pad_rows(logits.reshape(B * S, V)).unflatten(0, (B, S))
+
+
+def log_probs_per_token(logits, inputs):
+    """The log-probability of each label: ``logits`` bf16 (B, S, vocab_size) on the device, ``inputs`` int64 (B, S).  Returns fp32 (B, S - 1):
+    ``logits[b, s, inputs[b, s + 1]] - logsumexp(logits[b, s, :])``, all arithmetic in fp32 (not in bf16 as upstream).  One autograd node: the backward
+    writes the logits' gradient into a fresh buffer -- the logits stay the caller's.  ``S == 1`` gives an empty (B, 0) result without a launch."""
+    B, S, V = K.check_logits_ids(logits, inputs, "log_probs_per_token")
+    _device_only(logits, inputs)
+    if S == 1:
+        return torch.empty((B, 0), dtype=torch.float32, device=logits.device)
+    return O.LabelLogProbFn.apply(_vector_logits(logits), inputs, False)
+
+
+def log_probs_per_token_optimized(logits, inputs):
+    """``log_probs_per_token`` under the reference's other name: the same kernel.  Upstream this form (label logit minus logsumexp) is the one not to
+    use in bf16; here the subtraction runs in fp32 on an fp32 logsumexp, so that caveat does not apply."""
+    return log_probs_per_token(logits, inputs)
+
+
+def log_probs_per_seq(logprobs_per_token, loss_mask):
+    """The masked mean log-prob of each sequence, fp32 (B,); an empty mask gives NaN, as upstream."""
+    _device_only(logprobs_per_token, loss_mask)
+    return O.SeqMeanFn.apply(logprobs_per_token, loss_mask)
+
+
+def kl_div_per_token(policy_logprobs, reference_logprobs, policy_ratio=None):
+    """The k3 estimate of the KL per token, ``exp(ref - pol) - (ref - pol) - 1``; with ``policy_ratio`` (the unbiased estimate of DeepSeek-V3.2) times
+    that ratio, which then receives a gradient too."""
+    _device_only(policy_logprobs, reference_logprobs, policy_ratio)
+    return O.KlDivFn.apply(policy_logprobs, reference_logprobs, policy_ratio)
+
+
+def off_policy_seq_mask(kl_div_per_token, advantages, loss_mask, delta=0.5):
+    """The off-policy sequence mask of DeepSeek-V3.2, bool (B, 1): True unless the advantage is negative and the masked mean KL exceeds ``delta``."""
+    _device_only(kl_div_per_token, advantages, loss_mask)
+    return O.off_policy(kl_div_per_token, advantages, loss_mask, delta)[1]
+
+
+class GRPOLoss:
+    """The GRPO-family losses: hard-clipped surrogate (GRPO, DAPO, Dr. GRPO), soft gate (SAPO), sequence level (GSPO)."""
+
+    @staticmethod
+    def compute(
+        policy_ratio,
+        advantages,
+        loss_mask,
+        min_clip,
+        max_clip,
+        beta,
+        kl_div,
+        num_samples,
+        max_gen=1,
+        variant="grpo",
+        off_policy_mask=None,
+    ):
+        if variant == "gspo":
+            return GRPOLoss._compute_gspo_loss(policy_ratio, advantages, min_clip, max_clip, off_policy_mask)
+        if variant not in _TOKEN_LEVEL:
+            raise ValueError(f"Unknown loss type: {variant}")
+        _device_only(policy_ratio, advantages, loss_mask, kl_div, off_policy_mask)
+        return O.RatioLossFn.apply(policy_ratio, kl_div, advantages, loss_mask, min_clip, max_clip, beta, num_samples, max_gen, variant, off_policy_mask)
+
+    @staticmethod
+    def _compute_clipped_surrogate(policy_ratio, advantages_broadcast, min_clip, max_clip):
+        _device_only(policy_ratio, advantages_broadcast)
+        return O.SurrogateFn.apply(policy_ratio, advantages_broadcast, min_clip, max_clip, False)
+
+    @staticmethod
+    def _compute_sapo_surrogate(policy_ratio, advantages_broadcast, temp_pos_tokens=1.0, temp_neg_tokens=1.05):
+        _device_only(policy_ratio, advantages_broadcast)
+        return O.SurrogateFn.apply(policy_ratio, advantages_broadcast, temp_pos_tokens, temp_neg_tokens, True)
+
+    @staticmethod
+    def _compute_gspo_loss(masked_policy_ratio, advantages, min_clip, max_clip, off_policy_mask=None):
+        _device_only(masked_policy_ratio, advantages, off_policy_mask)
+        return O.GspoLossFn.apply(masked_policy_ratio, advantages, min_clip, max_clip, off_policy_mask)
+
+    @staticmethod
+    def _aggregate(loss_per_token, loss_mask, num_samples, max_gen, variant):
+        if variant not in _TOKEN_LEVEL:
+            raise ValueError(f"Unknown loss type: {variant}")
+        _device_only(loss_per_token, loss_mask)
+        return O.AggregateFn.apply(loss_per_token, loss_mask, num_samples, max_gen, variant)
+
+
+def grpo_policy_loss(logits, inputs, old_logprobs, reference_logprobs, advantages, loss_mask, num_samples, min_clip, max_clip, beta, max_gen=1,
+                     variant="grpo", unbiased_kl_estimate=False, off_policy_delta=None, inplace=True):
+    """The scalar GRPO loss of the policy's ``logits`` bf16 (B, S, vocab_size) for ``inputs`` int64 (B, S): what a training loop calls instead of the
+    reference's lines 1082-1111 (log-probs, ratio, KL, ``GRPOLoss.compute``).  ``old_logprobs`` / ``reference_logprobs`` fp32 (B, S - 1) come from
+    ``log_probs_per_token`` under ``torch.no_grad()``; ``advantages`` fp32 (B,); ``off_policy_delta``: the threshold of the off-policy sequence
+    mask, None for no mask.
+
+    With a token-level ``variant``, no off-policy mask and grad mode on, one kernel reads each logits row once, forms its loss term and overwrites it
+    with d loss / d logits.  THE LOGITS ARE CONSUMED with ``inplace=True`` (the default, as the LM-head loss does): after the call they hold their own
+    gradient, which ``backward()`` hands to the model.  ``inplace=False`` leaves them untouched and keeps the gradient in a fresh buffer.  GSPO and the
+    off-policy mask need a per-sequence quantity first and take the two-pass path (label log-probs, per-token chain, log-prob backward -- in place under
+    the same flag).  In no-grad mode only the forward runs.  ``backward()`` reads its incoming gradient once on the host to skip a pass over the logits
+    when it is exactly 1."""
+    B, S, V = K.check_logits_ids(logits, inputs, "grpo_policy_loss")
+    K.check_scalars(B, num_samples, max_gen, variant)
+    if S < 2:
+        raise ValueError("grpo_policy_loss: the sequences need at least two positions")
+    T = S - 1
+    old, ref = K._tok(old_logprobs, "old_logprobs", B, T), K._tok(reference_logprobs, "reference_logprobs", B, T)
+    adv = K._adv(advantages, B)
+    K.mask_operand(loss_mask, B, T)
+    _device_only(logits, inputs, old, ref, adv, loss_mask)
+    grad = torch.is_grad_enabled() and logits.requires_grad
+    args = (min_clip, max_clip, beta, num_samples, max_gen, variant, bool(unbiased_kl_estimate))
+    if not grad:
+        logp, _ = K.label_logprob_fwd(_vector_logits(logits.detach()), inputs)
+        return K.token_loss(logp, old, ref, adv, loss_mask, *args, delta=off_policy_delta, want_grad=False)[0]
+    lg = _vector_logits(logits)
+    if variant in _TOKEN_LEVEL and off_policy_delta is None:
+        return O.LogitsLossFn.apply(lg, inputs, old, ref, adv, loss_mask, *args, bool(inplace))[0]
+    logp = O.LabelLogProbFn.apply(lg, inputs, bool(inplace))
+    return O.TokenLossFn.apply(logp, old, ref, adv, loss_mask, *args, off_policy_delta)[0]
