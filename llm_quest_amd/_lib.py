@@ -166,6 +166,10 @@ SIGNATURES = {
     "mi355_grpo_token_loss": [_I, _L, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "mi355_grpo_piece": [_I, _I, _L, _P, _P, _P, _P, _P, _I, _F, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P],
     "mi355_grpo_logits_loss": [_I, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _P, _P, _P, _I, _F, _F, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    # GRPO losses from hidden states: the row work of a vocabulary-chunked LM head (csrc/grpo_head.hip)
+    "mi355_head_lse_chunk": [_L, _L, _L, _L, _P, _L, _P, _P, _P, _P, _I, _P],
+    "mi355_head_lse_finish": [_L, _P, _P, _P, _P, _P, _P],
+    "mi355_head_dlogits_chunk": [_L, _L, _L, _L, _L, _P, _P, _L, _P, _P, _P, _L, _P],
 }
 # size / constant queries: no stream argument, the return value is the answer (name -> (argtypes, restype))
 QUERIES = {

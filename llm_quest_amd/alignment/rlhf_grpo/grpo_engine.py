@@ -15,9 +15,16 @@ What differs from the reference, on purpose:
 Like the reference: a sequence whose mask is empty contributes 0 in the token-level variants; an empty mask gives NaN in ``log_probs_per_seq`` and so
 in GSPO.
 
+From the hidden states (this project's own names, csrc/grpo_head.hip): ``log_probs_per_token_from_hidden`` and ``grpo_policy_loss_from_hidden`` take the
+final-normed hidden states and the model's output head instead of logits and walk the head in vocabulary chunks, so the (B, S, vocab_size) logits -- held
+three times per batch by a loop on the functions above: the policy's and, under no-grad, the old and the reference policy's -- never exist.
+``Qwen3Model.label_log_probs`` is the one call a loop makes per policy.  The log-probs are those of the bf16 logits the head's GEMM would have written.
+
 Out of scope (not built here): sampling and generation inside the loop, the reward model and ``PrefRewardCalculator``, the collators,
 ``rlhf_grpo_training_loop``, the experimental loop and ``GRPOEvaluator``, DPO / RLVR / RPT (their log-prob needs are one call to
-``log_probs_per_token`` away), and fusing the LM-head GEMM into the log-prob pass (vocabulary-chunked, no logits in memory).
+``log_probs_per_token`` away); of the chunked head: a GEMM whose epilogue does the log-sum-exp (a chunk's logits never leaving the CU), skipping the
+rows whose ``loss_mask`` is 0, and a ``label_log_probs`` on the model classes other than ``Qwen3Model`` (the two functions themselves are
+model-agnostic: any ``forward_hidden`` and output head will do).
 """
 
 import torch
@@ -26,6 +33,7 @@ import torch.nn.functional as F
 from llm_quest_amd import _lib as L
 from llm_quest_amd import config
 from llm_quest_amd import kernels_grpo as K
+from llm_quest_amd import kernels_grpo_head as KH
 from llm_quest_amd import ops_grpo as O
 
 _TOKEN_LEVEL = ("grpo", "dapo", "dr_grpo", "sapo")
@@ -184,4 +192,52 @@ def grpo_policy_loss(logits, inputs, old_logprobs, reference_logprobs, advantage
     if variant in _TOKEN_LEVEL and off_policy_delta is None:
         return O.LogitsLossFn.apply(lg, inputs, old, ref, adv, loss_mask, *args, bool(inplace))[0]
     logp = O.LabelLogProbFn.apply(lg, inputs, bool(inplace))
+    return O.TokenLossFn.apply(logp, old, ref, adv, loss_mask, *args, off_policy_delta)[0]
+
+
+# ------------------------------------------------------------------------------------------------ from the hidden states: no logits in memory
+def _head_weight(out_head, what):
+    weight = getattr(out_head, "weight", None)
+    if not isinstance(weight, torch.Tensor):
+        raise TypeError(f"{what}: out_head must be the model's output head, a module with a bf16 ``weight`` (vocab_size, emb_dim)")
+    return weight
+
+
+def log_probs_per_token_from_hidden(hidden, out_head, inputs, vocab_chunk=None):
+    """What ``log_probs_per_token(out_head(hidden), inputs)`` defines, fp32 (B, S - 1), without the logits: ``hidden`` bf16 (B, S, emb_dim) are the
+    final-normed hidden states (``forward_hidden``), ``out_head`` the model's output head (a module with a bf16 ``weight`` (vocab_size, emb_dim) that its
+    arena knows; tied or not).  The head is walked in chunks of ``vocab_chunk`` columns (a positive multiple of 8; None: ``KH.head_chunks``' default): one
+    GEMM writes a chunk's bf16 logits, a row kernel folds them into an online log-sum-exp, and the backward recomputes each chunk -- 4 / 3 of the head's
+    GEMM work for (B, S, vocab_size) less memory, three times per batch.  ``S == 1`` gives an empty (B, 0) result without a launch."""
+    weight = _head_weight(out_head, "log_probs_per_token_from_hidden")
+    B, S, D, V = KH.check_head(hidden, weight, inputs, "log_probs_per_token_from_hidden")
+    KH.head_chunks(B * S, V, vocab_chunk)
+    _device_only(hidden, weight, inputs)
+    if S == 1:
+        return torch.empty((B, 0), dtype=torch.float32, device=hidden.device)
+    if not (torch.is_grad_enabled() and (hidden.requires_grad or weight.requires_grad)):
+        return KH.head_logprob_fwd(hidden.detach(), weight.detach(), inputs, vocab_chunk)[0]
+    return O.HeadLogProbFn.apply(hidden, inputs, out_head, weight, vocab_chunk)
+
+
+def grpo_policy_loss_from_hidden(hidden, out_head, inputs, old_logprobs, reference_logprobs, advantages, loss_mask, num_samples, min_clip, max_clip, beta,
+                                 max_gen=1, variant="grpo", unbiased_kl_estimate=False, off_policy_delta=None, vocab_chunk=None):
+    """``grpo_policy_loss`` from the policy's hidden states instead of its logits: ``log_probs_per_token_from_hidden``, then the per-token chain as one
+    node.  All five variants and the off-policy mask take this one path: every per-sequence quantity is known before the backward walks the head's
+    chunks.  Nothing is consumed; the other operands are those of ``grpo_policy_loss``.  In no-grad mode only the forward runs."""
+    weight = _head_weight(out_head, "grpo_policy_loss_from_hidden")
+    B, S, D, V = KH.check_head(hidden, weight, inputs, "grpo_policy_loss_from_hidden")
+    KH.head_chunks(B * S, V, vocab_chunk)
+    K.check_scalars(B, num_samples, max_gen, variant)
+    if S < 2:
+        raise ValueError("grpo_policy_loss_from_hidden: the sequences need at least two positions")
+    T = S - 1
+    old, ref = K._tok(old_logprobs, "old_logprobs", B, T), K._tok(reference_logprobs, "reference_logprobs", B, T)
+    adv = K._adv(advantages, B)
+    K.mask_operand(loss_mask, B, T)
+    _device_only(hidden, weight, inputs, old, ref, adv, loss_mask)
+    args = (min_clip, max_clip, beta, num_samples, max_gen, variant, bool(unbiased_kl_estimate))
+    logp = log_probs_per_token_from_hidden(hidden, out_head, inputs, vocab_chunk)
+    if not logp.requires_grad:
+        return K.token_loss(logp, old, ref, adv, loss_mask, *args, delta=off_policy_delta, want_grad=False)[0]
     return O.TokenLossFn.apply(logp, old, ref, adv, loss_mask, *args, off_policy_delta)[0]

@@ -1,11 +1,14 @@
-"""Autograd nodes of the GRPO loss layer on the launchers of ``kernels_grpo.py``: the label log-probs over the logits, the per-token chain as one
-node, the one-pass logits loss, and one small node per reference-named per-token function.  The kernels write the gradients; a node's backward hands
+"""Autograd nodes of the GRPO loss layer on the launchers of ``kernels_grpo.py`` / ``kernels_grpo_head.py``: the label log-probs over the logits, the
+same from the hidden states on a vocabulary-chunked LM head, the per-token chain as one node, the one-pass logits loss, and one small node per
+reference-named per-token function.  The kernels write the gradients; a node's backward hands
 them on, times the incoming gradient where that is not known to be one."""
 
 import torch
 
 from . import kernels as K0
 from . import kernels_grpo as K
+from . import kernels_grpo_head as KH
+from .ops import arena_for
 
 F32 = torch.float32
 
@@ -42,6 +45,30 @@ class LabelLogProbFn(torch.autograd.Function):
         g = g.to(F32)
         dl = K.label_logprob_bwd(g if g.is_contiguous() else g.contiguous(), logits, lse, ids, out=logits if ctx.inplace else None)
         return dl.detach(), None, None
+
+
+class HeadLogProbFn(torch.autograd.Function):
+    """``log_probs_per_token_from_hidden``: fp32 [B, S - 1] from bf16 hidden states [B, S, D], int64 ids [B, S] and the (possibly tied) head weight of
+    ``owner``, chunk by chunk; the logits are never held.  Backward walks the chunks again: dh comes back, the weight's gradient goes to the owner's
+    arena (accumulating where the embedding's backward shares it).  The incoming gradient is a weight per token and is multiplied in by the kernel."""
+
+    @staticmethod
+    def forward(ctx, hidden, ids, owner, weight, vocab_chunk):
+        arena_for(owner)
+        logp, lse = KH.head_logprob_fwd(hidden, weight, ids, vocab_chunk)
+        ctx.saved = (hidden, ids, lse)
+        ctx.owner, ctx.weight, ctx.vocab_chunk = owner, weight, vocab_chunk
+        return logp
+
+    @staticmethod
+    def backward(ctx, g):
+        hidden, ids, lse = ctx.saved
+        ctx.saved = None
+        w = ctx.weight
+        view, acc = arena_for(ctx.owner).grad_target(w) if w.requires_grad else (None, False)
+        g = g.to(F32)
+        dh = KH.head_logprob_bwd(g if g.is_contiguous() else g.contiguous(), hidden, w, lse, ids, ctx.vocab_chunk, dw_out=view, dw_accumulate=acc)
+        return dh, None, None, None, None
 
 
 class TokenLossFn(torch.autograd.Function):

@@ -117,6 +117,14 @@ class Qwen3Model(nn.Module):
             return ops_decode.qwen3_forward_cached(self, x, kv_cache, attn_mask, position_ids, input_embedded)
         return self.out_head(self.forward_hidden(x, attn_mask, position_ids, input_embedded))
 
+    def label_log_probs(self, x, attn_mask=None, position_ids=None, vocab_chunk=None):
+        """The log-probability of each label, fp32 (b, s - 1), without the (b, s, vocab) logits: ``forward_hidden``, then the output head walked in
+        vocabulary chunks (``grpo_engine.log_probs_per_token_from_hidden``).  The one call an RL loop makes per policy: under ``torch.no_grad()`` for
+        the old and the reference policy, in grad mode for the policy itself."""
+        from llm_quest_amd.alignment.rlhf_grpo.grpo_engine import log_probs_per_token_from_hidden
+
+        return log_probs_per_token_from_hidden(self.forward_hidden(x, attn_mask, position_ids), self.out_head, x, vocab_chunk)
+
     def lm_loss(self, hidden_rows, targets):
         """Mean CE (ignore_index=-100) of the tied head on ``hidden_rows`` (rows, emb) vs ``targets`` (rows,)."""
         self._build_arenas()
@@ -135,6 +143,10 @@ class Qwen3MoEModel(Qwen3Model):
         if cfg.get("gradient_checkpointing", False):
             raise NotImplementedError("Qwen3MoEModel: gradient_checkpointing=True is not built for mixture-of-experts blocks")
         super().__init__(cfg)  # the dense model's construction with MoE blocks (upstream builds the dense blocks first and swaps them)
+
+    def label_log_probs(self, x, attn_mask=None, position_ids=None, vocab_chunk=None):
+        raise NotImplementedError("Qwen3MoEModel: label_log_probs is built for the dense Qwen3Model; call log_probs_per_token_from_hidden on the "
+                                  "final-normed hidden states and out_head yourself")
 
     def forward(self, x, attn_mask=None, kv_cache=None, position_ids=None, gate_probas=None, return_gate_probas=False):
         """Logits (b, s, vocab); with ``return_gate_probas`` also the list of every layer's (b*s, num_experts) gate probabilities.
