@@ -170,6 +170,12 @@ SIGNATURES = {
     "mi355_head_lse_chunk": [_L, _L, _L, _L, _P, _L, _P, _P, _P, _P, _I, _P],
     "mi355_head_lse_finish": [_L, _P, _P, _P, _P, _P, _P],
     "mi355_head_dlogits_chunk": [_L, _L, _L, _L, _L, _P, _P, _L, _P, _P, _P, _L, _P],
+    # Preference tuning: DPO's sequence average and loss, the reward model's pooling with the head folded in (csrc/preference.hip)
+    "mi355_dpo_seq_logprob": [_I, _L, _P, _P, _I, _P, _P, _P],
+    "mi355_dpo_seq_logprob_bwd": [_I, _L, _P, _P, _I, _P, _P, _P],
+    "mi355_dpo_loss": [_I, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P],
+    "mi355_reward_pool_fwd": [_I, _I, _L, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],
+    "mi355_reward_pool_bwd": [_I, _I, _L, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P],
 }
 # size / constant queries: no stream argument, the return value is the answer (name -> (argtypes, restype))
 QUERIES = {

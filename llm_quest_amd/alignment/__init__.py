@@ -1,1 +1,1 @@
-"""Alignment (reference: llm_quest/alignment): the GRPO loss layer of ``rlhf_grpo``."""
+"""Alignment (reference: llm_quest/alignment): the GRPO loss layer and the reward model of ``rlhf_grpo``, DPO in ``dpo``."""

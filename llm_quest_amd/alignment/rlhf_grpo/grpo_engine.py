@@ -20,12 +20,21 @@ final-normed hidden states and the model's output head instead of logits and wal
 three times per batch by a loop on the functions above: the policy's and, under no-grad, the old and the reference policy's -- never exist.
 ``Qwen3Model.label_log_probs`` is the one call a loop makes per policy.  The log-probs are those of the bf16 logits the head's GEMM would have written.
 
-Out of scope (not built here): sampling and generation inside the loop, the reward model and ``PrefRewardCalculator``, the collators,
-``rlhf_grpo_training_loop``, the experimental loop and ``GRPOEvaluator``, DPO / RLVR / RPT (their log-prob needs are one call to
-``log_probs_per_token`` away); of the chunked head: a GEMM whose epilogue does the log-sum-exp (a chunk's logits never leaving the CU), skipping the
+The reward model's side (csrc/preference.hip): ``PrefRewardCalculator`` pools a backbone's hidden states into one score per sequence with the head's
+``Linear(emb_dim, 1)`` folded into the kernel -- one pass over the hidden states, fp32 accumulation, fp32 ``(b,)`` scores, the gradients of the hidden states,
+the weight and the bias from its backward; ``scores_mean_pooling_from_hidden`` is this project's own name for the reference reward model's default pooling
+without the ``(b, s, 1)`` intermediate and without an N = 1 GEMM.  ``evaluate_reward_model`` and ``reward_model_training_eval_loop_simple`` are the
+reference's loops; the models here are bf16 themselves, so the loops carry no autocast context.  The reward model is any module called as
+``reward_model(ids, attn_mask=..., reward_mask=...)`` that returns ``(b,)`` scores (the reference's GPT-2-based ``PreferenceRewardModel`` is not built).
+
+Out of scope (not built here): sampling and generation inside the loop, ``PreferenceRewardModel`` (GPT-2 is CPU plumbing here), the RLHF collators,
+``rlhf_grpo_training_loop``, the experimental loop and ``GRPOEvaluator``, RLVR / RPT (their log-prob needs are one call to ``log_probs_per_token``
+away; DPO is in ``alignment/dpo/dpo.py``); of the chunked head: a GEMM whose epilogue does the log-sum-exp (a chunk's logits never leaving the CU), skipping the
 rows whose ``loss_mask`` is 0, and a ``label_log_probs`` on the model classes other than ``Qwen3Model`` (the two functions themselves are
 model-agnostic: any ``forward_hidden`` and output head will do).
 """
+
+import os
 
 import torch
 import torch.nn.functional as F
@@ -34,7 +43,10 @@ from llm_quest_amd import _lib as L
 from llm_quest_amd import config
 from llm_quest_amd import kernels_grpo as K
 from llm_quest_amd import kernels_grpo_head as KH
+from llm_quest_amd import kernels_pref as KP
 from llm_quest_amd import ops_grpo as O
+from llm_quest_amd import ops_pref as OP
+from llm_quest_amd.utils import CheckpointEvaluator
 
 _TOKEN_LEVEL = ("grpo", "dapo", "dr_grpo", "sapo")
 
@@ -42,6 +54,131 @@ _TOKEN_LEVEL = ("grpo", "dapo", "dr_grpo", "sapo")
 def bt_loss(chosen_logits, rejected_logits, beta=1.0):
     """Bradley-Terry loss of the reward model: mean over the batch of -log sigmoid(beta (chosen - rejected)).  ``B`` numbers: plain torch."""
     return -F.logsigmoid(beta * (chosen_logits - rejected_logits)).mean()
+
+
+class PrefRewardCalculator:
+    """The ways to turn a reward model's output into one score per sequence, fp32 (b,), each one kernel (csrc/preference.hip):
+
+    - ``scores_mean_pooling``: the masked mean of the head's per-token scores (b, s, 1);
+    - ``hidden_states_mean_pooling``: the head on the masked mean of the hidden states;
+    - ``last_token_score``: the head on the hidden state of the last real token;
+    - ``scores_mean_pooling_from_hidden``: ``scores_mean_pooling(model_head(hidden_states), reward_mask)`` from the hidden states themselves.
+
+    ``hidden_states`` are bf16 or fp32 (b, s, emb_dim) on the device, emb_dim a multiple of 8 up to 8 192; ``model_head`` is an ``nn.Linear(emb_dim, 1)`` with or
+    without bias, its parameters bf16 or fp32 whatever the hidden states are; the masks are (b, s) of 0 / 1 in bool, an integer type or a float type.  Rows
+    whose mask is 0 are not read, and their gradient is exact zeros."""
+
+    @staticmethod
+    def scores_mean_pooling(rewards, reward_mask):
+        """``sum(rewards * reward_mask) / max(count, 1)``; an empty mask gives 0."""
+        _pool_operands("PrefRewardCalculator.scores_mean_pooling", rewards, reward_mask, None, 0)
+        return OP.RewardPoolFn.apply(rewards, reward_mask, None, None, 0)
+
+    @staticmethod
+    def hidden_states_mean_pooling(hidden_states, reward_mask, model_head):
+        """``model_head(sum(hidden_states * reward_mask) / max(count, 1))``; an empty mask gives the head's bias."""
+        w, b = _pool_operands("PrefRewardCalculator.hidden_states_mean_pooling", hidden_states, reward_mask, model_head, 1)
+        return OP.RewardPoolFn.apply(hidden_states, reward_mask, w, b, 1)
+
+    @staticmethod
+    def last_token_score(hidden_states, attention_mask, model_head):
+        """``model_head(hidden_states[b, attention_mask[b].sum() - 1])``; a count of 0 selects row ``s - 1`` (upstream's index -1)."""
+        w, b = _pool_operands("PrefRewardCalculator.last_token_score", hidden_states, attention_mask, model_head, 2)
+        return OP.RewardPoolFn.apply(hidden_states, attention_mask, w, b, 2)
+
+    @staticmethod
+    def scores_mean_pooling_from_hidden(hidden_states, reward_mask, model_head):
+        """``sum_t reward_mask (hidden_states_t . w + bias) / max(count, 1)``: the per-token scores are never written; an empty mask gives 0."""
+        w, b = _pool_operands("PrefRewardCalculator.scores_mean_pooling_from_hidden", hidden_states, reward_mask, model_head, 3)
+        return OP.RewardPoolFn.apply(hidden_states, reward_mask, w, b, 3)
+
+
+def _pool_operands(what, hidden, mask, model_head, mode):
+    """The refusals shared by the four pooling functions, host side first; returns the head's (weight, bias)."""
+    w = b = None
+    if mode != 0:
+        w, b = getattr(model_head, "weight", None), getattr(model_head, "bias", None)
+        if not isinstance(w, torch.Tensor):
+            raise TypeError(f"{what}: model_head must be an nn.Linear(emb_dim, 1)")
+    try:
+        B, S, E = KP.check_hidden(hidden, mask, mode, "rewards" if mode == 0 else "hidden_states")
+        KP.mask_operand(mask, (B, S), "the mask")
+        if mode != 0:
+            KP.check_head(w, b, E)
+    except (TypeError, ValueError) as e:
+        raise type(e)(f"{what}: {e}") from None
+    _device_only(hidden, mask, w, b)
+    return w, b
+
+
+def evaluate_reward_model(val_loader, reward_model, eval_num_batches=None, beta=1.0):
+    """(average Bradley-Terry loss per batch, share of pairs whose chosen score exceeds the rejected one) over the first ``eval_num_batches`` batches of
+    ``val_loader`` (None: all of it), in eval mode and without gradients; the model is put back in train mode."""
+    total_loss, correct, count = 0.0, 0, 0
+    num_batches_to_eval = min(eval_num_batches, len(val_loader)) if eval_num_batches else len(val_loader)
+    reward_model.eval()
+    with torch.no_grad():  # upstream: inference_mode; the models here keep lazily built device buffers, which must stay usable by the next training step
+        for i, batch in enumerate(val_loader):
+            if i >= num_batches_to_eval:
+                break
+            pref_rewards = reward_model(batch["chosen"], attn_mask=batch["chosen_attn_mask"], reward_mask=batch["chosen_mask"])
+            rej_rewards = reward_model(batch["rejected"], attn_mask=batch["rejected_attn_mask"], reward_mask=batch["rejected_mask"])
+            total_loss += bt_loss(pref_rewards, rej_rewards, beta=beta).item()
+            correct += (pref_rewards > rej_rewards).sum().item()
+            count += pref_rewards.shape[0]
+    reward_model.train()
+    return total_loss / num_batches_to_eval, correct / count
+
+
+def reward_model_training_eval_loop_simple(
+    train_loader,
+    val_loader,
+    reward_model,
+    optimizer,
+    num_epoch,
+    eval_freq,
+    eval_num_batches=None,
+    beta=1.0,
+):
+    """Train ``reward_model`` on ``pref_reward_collate`` batches with the Bradley-Terry loss.  Every ``eval_freq`` steps: the interval's training loss and
+    accuracy, ``evaluate_reward_model`` on ``eval_num_batches`` batches, and -- when ``CheckpointEvaluator.is_rm_accu_best`` says so -- the model's
+    ``state_dict`` saved under ``config.rlhf_grpo_checkpoint_dir``.  Returns the tracked metrics."""
+    step = 0
+    interval_loss, interval_correct, interval_count = 0.0, 0, 0
+    tracking = {"train_losses": [], "val_losses": [], "train_acc": [], "val_acc": []}
+    chkp_eval = CheckpointEvaluator()
+    reward_model.train()
+    for epoch in range(1, num_epoch + 1):
+        for batch in train_loader:
+            step += 1
+            pref_rewards = reward_model(batch["chosen"], attn_mask=batch["chosen_attn_mask"], reward_mask=batch["chosen_mask"])
+            rej_rewards = reward_model(batch["rejected"], attn_mask=batch["rejected_attn_mask"], reward_mask=batch["rejected_mask"])
+            loss = bt_loss(pref_rewards, rej_rewards, beta=beta)
+            loss.backward()
+            optimizer.step()
+            optimizer.zero_grad()
+            interval_loss += loss.item()
+            interval_correct += (pref_rewards > rej_rewards).sum().item()
+            interval_count += pref_rewards.shape[0]
+            if step % eval_freq == 0:
+                train_loss = interval_loss / eval_freq
+                train_acc = interval_correct / interval_count if interval_count > 0 else 0.0
+                val_loss, val_acc = evaluate_reward_model(val_loader, reward_model, eval_num_batches, beta=beta)
+                tracking["train_losses"].append(train_loss)  # upstream declares the two training lists and leaves them empty
+                tracking["train_acc"].append(train_acc)
+                tracking["val_losses"].append(val_loss)
+                tracking["val_acc"].append(val_acc)
+                print(
+                    f"Epoch: {epoch}, Step: {step} |",
+                    f"T. loss: {train_loss:.5f}, V. loss: {val_loss:.5f} |",
+                    f"T. acc: {train_acc * 100:.2f}%, V. acc: {val_acc * 100:.2f}%",
+                )
+                if chkp_eval.is_rm_accu_best(val_acc, val_loss):
+                    os.makedirs(config.rlhf_grpo_checkpoint_dir, exist_ok=True)
+                    name = f"best_rm_checkpoint_{step}_accu_{chkp_eval.max_accu_pref_rm:.3f}_loss_{val_loss:.3f}.pt"
+                    torch.save(reward_model.state_dict(), os.path.join(config.rlhf_grpo_checkpoint_dir, name))
+                interval_loss, interval_correct, interval_count = 0.0, 0, 0
+    return tracking
 
 
 def z_scores(rewards, num_samples, dr_grpo=None):

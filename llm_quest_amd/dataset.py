@@ -210,3 +210,57 @@ class MultimodalDataset(torch.utils.data.Dataset):
                 t.record_stream(torch.cuda.current_stream(self.device))
             yield batch
             del keep
+
+
+# ----------------------------------------------------------------------------------------------------------------- preference pairs
+def _pad_pairs(batch, pad_token_id, allowed_max_length, append_eos):
+    """The host-side list work both preference collates share: the common length (longest of all chosen and rejected sequences + 1, capped by
+    ``allowed_max_length``), the sequences cut to it, and per sample (prompt length, chosen length, rejected length) after the cut."""
+    if not batch:
+        raise ValueError("a preference batch needs at least one sample")
+    tail = [pad_token_id] if append_eos else []
+    width = max(max(len(item["chosen"]), len(item["rejected"])) for item in batch) + 1
+    if allowed_max_length is not None:
+        width = min(width, allowed_max_length)
+    rows = {"chosen": [], "rejected": []}
+    lens = []
+    for item in batch:
+        cut = {k: (item[k] + tail)[:width] if allowed_max_length is not None else item[k] + tail for k in rows}
+        for k in rows:
+            rows[k].append(cut[k] + [pad_token_id] * (width - len(cut[k])))
+        lens.append((len(item["prompt"]), len(cut["chosen"]), len(cut["rejected"])))
+    return width, rows, lens
+
+
+def dpo_collate(
+    batch,
+    pad_token_id=50256,
+    allowed_max_length=None,
+    mask_prompt_tokens=True,
+    device=torch.device("cpu"),
+):
+    """Collate function of DPO training (reference dataset.py:899-978).  ``batch``: a list of ``{"prompt", "chosen", "rejected"}`` token-id lists, chosen
+    and rejected including the prompt.  Returns ``chosen`` / ``rejected`` int64 (b, s) padded with ``pad_token_id`` to one common length -- the longest
+    sequence + 1 for the label shift, at most ``allowed_max_length`` -- and ``chosen_mask`` / ``rejected_mask`` bool (b, s): True on real tokens, and
+    with ``mask_prompt_tokens`` not on the prompt.  The list work runs on the host; the four tensors are created on ``device``."""
+    width, rows, lens = _pad_pairs(batch, pad_token_id, allowed_max_length, append_eos=False)
+    first = [p if mask_prompt_tokens else 0 for p, _, _ in lens]
+    masks = {"chosen": [[first[i] <= t < c for t in range(width)] for i, (_, c, _) in enumerate(lens)],
+             "rejected": [[first[i] <= t < r for t in range(width)] for i, (_, _, r) in enumerate(lens)]}
+    out = {k: torch.tensor(rows[k], dtype=torch.long, device=device).reshape(len(batch), width) for k in rows}
+    out.update({f"{k}_mask": torch.tensor(masks[k], dtype=torch.bool, device=device).reshape(len(batch), width) for k in rows})
+    return out
+
+
+def pref_reward_collate(batch, pad_token_id=50256, allowed_max_length=None, device=torch.device("cpu")):
+    """Collate function of reward-model training on preference pairs (reference dataset.py:982-1070).  Like ``dpo_collate``, but every sequence gets
+    ``pad_token_id`` appended as its EoS token before the cut (the + 1 of the common length is that token), and two masks per side come back:
+    ``chosen_attn_mask`` / ``rejected_attn_mask`` bool (b, s), True on real tokens including the EoS, and ``chosen_mask`` / ``rejected_mask``, the
+    reward masks: the attention mask without the prompt."""
+    width, rows, lens = _pad_pairs(batch, pad_token_id, allowed_max_length, append_eos=True)
+    out = {k: torch.tensor(rows[k], dtype=torch.long, device=device).reshape(len(batch), width) for k in rows}
+    for k, col in (("chosen", 1), ("rejected", 2)):
+        out[f"{k}_mask"] = torch.tensor([[n[0] <= t < n[col] for t in range(width)] for n in lens], dtype=torch.bool, device=device).reshape(len(batch), width)
+    for k, col in (("chosen", 1), ("rejected", 2)):
+        out[f"{k}_attn_mask"] = torch.tensor([[t < n[col] for t in range(width)] for n in lens], dtype=torch.bool, device=device).reshape(len(batch), width)
+    return out

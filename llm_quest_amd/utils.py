@@ -251,3 +251,55 @@ def report_loading_status(model, load_result, converted_weights):
         print("-> out_head is expected here with tie_embeddings=True, and so are the locally rebuilt buffers (mask, cos, sin)\n")
     if load_result.unexpected_keys:
         print(f"Unexpected keys: {load_result.unexpected_keys}")
+
+
+class CheckpointEvaluator:
+    """Decides whether a checkpoint is the best so far and worth saving (reference utils.py:323-394): RLHF / RLVR GRPO training by the KL-penalised reward,
+    reward-model training by the validation accuracy.  Plain Python on host numbers."""
+
+    def __init__(
+        self,
+        kl_div_threshold=0.5,
+        min_reward_threshold=6.0,
+        beta=1.0,
+        rm_min_accuracy_threshold=0.9,
+        rm_min_val_loss_threshold=0.1,
+    ):
+        """``kl_div_threshold`` / ``min_reward_threshold``: a GRPO checkpoint qualifies only with a KL at most the first and a reward at least the
+        second; ``beta`` weighs the KL in its score.  ``rm_min_accuracy_threshold`` / ``rm_min_val_loss_threshold``: a reward-model checkpoint qualifies only
+        with an accuracy at least the first and a validation loss at most the second."""
+        self.kl_div_threshold = kl_div_threshold
+        self.min_reward_threshold = min_reward_threshold
+        self.beta = beta
+        self.max_score_grpo = float("-inf")
+        self.max_accu_pref_rm = float("-inf")
+        self.rm_min_accuracy_threshold = rm_min_accuracy_threshold
+        self.rm_min_val_loss_threshold = rm_min_val_loss_threshold
+
+    def _is_grpo_best(self, kl_div, reward):
+        if kl_div > self.kl_div_threshold or reward < self.min_reward_threshold:
+            return False
+        score = reward - self.beta * kl_div
+        if score <= self.max_score_grpo:
+            return False
+        print(f"New max score found {score:.3f} - saving checkpoint")
+        self.max_score_grpo = score
+        return True
+
+    def is_rlhf_grpo_best(self, kl_div, reward):
+        """True when ``reward - beta * kl_div`` of a qualifying checkpoint exceeds every score seen so far (which it then replaces)."""
+        return self._is_grpo_best(kl_div, reward)
+
+    def is_rm_accu_best(self, accuracy, val_loss):
+        """True when the accuracy of a qualifying checkpoint exceeds every accuracy seen so far (which it then replaces)."""
+        if accuracy < self.rm_min_accuracy_threshold or val_loss > self.rm_min_val_loss_threshold:
+            return False
+        if accuracy <= self.max_accu_pref_rm:
+            return False
+        print(f"New max accuracy found {accuracy:.3f} - saving checkpoint")
+        self.max_accu_pref_rm = accuracy
+        return True
+
+    def is_rlvr_grpo_best(self, kl_div, reward):
+        """The rule of ``is_rlhf_grpo_best`` under RLVR's name; the two share ``max_score_grpo``, as upstream."""
+        return self._is_grpo_best(kl_div, reward)
