@@ -176,6 +176,9 @@ SIGNATURES = {
     "mi355_dpo_loss": [_I, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P],
     "mi355_reward_pool_fwd": [_I, _I, _L, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],
     "mi355_reward_pool_bwd": [_I, _I, _L, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P],
+    # Rollout sampling: temperature / top-k / top-p / min-p rows with the rollout's per-token bookkeeping, the response masks (csrc/sampling.hip)
+    "mi355_sample_rows": [_L, _L, _P, _I, _L, _I, _I, _F, _F, _F, _P, _U, _U, _P, _P, _P, _I, _L, _P, _L, _P, _L, _L, _P, _P],
+    "mi355_response_masks": [_L, _L, _L, _P, _L, _P, _L, _P, _I, _L, _P, _P, _P],
 }
 # size / constant queries: no stream argument, the return value is the answer (name -> (argtypes, restype))
 QUERIES = {

@@ -27,9 +27,18 @@ without the ``(b, s, 1)`` intermediate and without an N = 1 GEMM.  ``evaluate_re
 reference's loops; the models here are bf16 themselves, so the loops carry no autocast context.  The reward model is any module called as
 ``reward_model(ids, attn_mask=..., reward_mask=...)`` that returns ``(b,)`` scores (the reference's GPT-2-based ``PreferenceRewardModel`` is not built).
 
-Out of scope (not built here): sampling and generation inside the loop, ``PreferenceRewardModel`` (GPT-2 is CPU plumbing here), the RLHF collators,
-``rlhf_grpo_training_loop``, the experimental loop and ``GRPOEvaluator``, RLVR / RPT (their log-prob needs are one call to ``log_probs_per_token``
-away; DPO is in ``alignment/dpo/dpo.py``); of the chunked head: a GEMM whose epilogue does the log-sum-exp (a chunk's logits never leaving the CU), skipping the
+The RLHF loop (csrc/sampling.hip for its rollouts): ``rlhf_grpo_prompt_collator``, ``batched_responses_collator``, ``rlhf_grpo_training_loop`` and
+``GRPOEvaluator`` carry the reference's names, parameter order and defaults.  The rollouts come from ``generate.generate_batched_rollouts`` (one sampling
+launch per token that also keeps the loop's books, no ``torch.cat`` per token); the response masks are one integer kernel; a model that offers
+``label_log_probs`` (or ``forward_hidden`` and ``out_head``) takes the vocabulary-chunked head, so the (B, S, vocab_size) logits do not exist three times per
+batch, any other model takes ``log_probs_per_token`` / ``grpo_policy_loss`` on its logits.  Trailing keyword extensions: ``rng`` (a ``generate.SampleRNG``),
+``sync_every`` (how often the rollout loop reads the device) and ``vocab_chunk``.  The old / reference log-probs and the rewards run under
+``torch.no_grad()`` where upstream has ``inference_mode``, for the reason given at ``evaluate_reward_model``.
+
+Out of scope (not built here): ``PreferenceRewardModel`` (GPT-2 is CPU plumbing here), the experimental loop
+(``grpo_training_loop_variant_experimental``), RLVR / RPT and ``VerifiableRewardCalculator`` (string and tokenizer work; their log-prob needs are one call
+to ``log_probs_per_token`` away; DPO is in ``alignment/dpo/dpo.py``), left-padded rollouts, hipGraph capture of the sampled step; of the chunked head: a GEMM
+whose epilogue does the log-sum-exp (a chunk's logits never leaving the CU), skipping the
 rows whose ``loss_mask`` is 0, and a ``label_log_probs`` on the model classes other than ``Qwen3Model`` (the two functions themselves are
 model-agnostic: any ``forward_hidden`` and output head will do).
 """
@@ -44,8 +53,10 @@ from llm_quest_amd import config
 from llm_quest_amd import kernels_grpo as K
 from llm_quest_amd import kernels_grpo_head as KH
 from llm_quest_amd import kernels_pref as KP
+from llm_quest_amd import kernels_sample as KS
 from llm_quest_amd import ops_grpo as O
 from llm_quest_amd import ops_pref as OP
+from llm_quest_amd.generate import generate_batched_rollouts
 from llm_quest_amd.utils import CheckpointEvaluator
 
 _TOKEN_LEVEL = ("grpo", "dapo", "dr_grpo", "sapo")
@@ -378,3 +389,293 @@ def grpo_policy_loss_from_hidden(hidden, out_head, inputs, old_logprobs, referen
     if not logp.requires_grad:
         return K.token_loss(logp, old, ref, adv, loss_mask, *args, delta=off_policy_delta, want_grad=False)[0]
     return O.TokenLossFn.apply(logp, old, ref, adv, loss_mask, *args, off_policy_delta)[0]
+
+
+# ------------------------------------------------------------------------------------------------ the RLHF loop: collators, training loop, evaluator
+def rlhf_grpo_prompt_collator(prompts, pad_token_id=50256, custom_max_length=None, device=torch.device("cpu")):
+    """Pad a list of prompts (lists of token ids) to one length on the right: ``padded_prompts`` int64 (b, max_len), ``prompt_masks`` bool of the same
+    shape (False on the padding) and ``last_real_pos`` int64 (b,), the index of each prompt's last real token.  ``custom_max_length`` truncates.  Host list
+    work."""
+    longest = max(len(sample) for sample in prompts)
+    if custom_max_length is not None:
+        prompts = [sample[:custom_max_length] for sample in prompts]
+        longest = min(longest, custom_max_length)
+    padded = [sample + [pad_token_id] * (longest - len(sample)) for sample in prompts]
+    masks = [[True] * len(sample) + [False] * (longest - len(sample)) for sample in prompts]
+    last = [len(sample) - 1 for sample in prompts]
+    return {
+        "padded_prompts": torch.tensor(padded).to(device),
+        "prompt_masks": torch.tensor(masks, dtype=torch.bool).to(device),
+        "last_real_pos": torch.tensor(last, dtype=torch.long).to(device),
+    }
+
+
+def batched_responses_collator(responses, prompt_masks, device="cuda", eos_ids=50256, pad_token_id=50256):
+    """The masks of a batch of rollouts, one integer kernel (csrc/sampling.hip): ``responses`` int64 (b, prompt_len + generated) and ``prompt_masks`` bool
+    (b, prompt_len) on the device.  ``attn_masks``: the prompt as ``prompt_masks`` has it, the response up to and including its first EOS / pad token
+    (upstream's ``cumsum <= 1``: every column before the SECOND stop token, which in a rollout directly follows the first); ``reward_masks``: the same with
+    the prompt cleared; ``padded_responses``: the responses themselves.  Trailing all-pad columns (``sync_every > 1``) are masked like any padding."""
+    attn, reward = KS.response_masks(responses, prompt_masks, eos_ids, pad_token_id)
+    return {"padded_responses": responses.to(device), "reward_masks": reward.to(device), "attn_masks": attn.to(device)}
+
+
+def _policy_label_log_probs(model, ids, attn_mask, vocab_chunk):
+    """fp32 (B, S - 1) label log-probs of ``model``: through the vocabulary-chunked head where the model offers it, else from its logits."""
+    if _has_hidden_path(model):
+        return log_probs_per_token_from_hidden(model.forward_hidden(ids, attn_mask), model.out_head, ids, vocab_chunk)
+    return log_probs_per_token(logits=model(ids, attn_mask), inputs=ids)
+
+
+def _has_hidden_path(model):
+    if type(model).__name__ == "Qwen3MoEModel":  # its blocks keep auxiliary state per forward; the logits path is the one it is tested on
+        return False
+    return callable(getattr(model, "forward_hidden", None)) and isinstance(getattr(getattr(model, "out_head", None), "weight", None), torch.Tensor)
+
+
+def _build_lazy_buffers(*models):
+    """The models here build device buffers on their first forward: that must not happen inside the rollouts' ``inference_mode``."""
+    for model in models:
+        for m in model.modules() if isinstance(model, torch.nn.Module) else ():
+            build = getattr(m, "_build_arenas", None)
+            if callable(build):
+                build()
+
+
+def rlhf_grpo_training_loop(
+    train_loader,
+    val_loader,
+    policy_model,
+    reference_model,
+    reward_model,
+    optimizer,
+    num_epoch,
+    num_samples,
+    num_grad_updates,
+    policy_config,
+    device,
+    max_gen=35,
+    min_clip_eps=0.2,
+    max_clip_eps=0.2,
+    beta=1.0,
+    unbiased_kl_estimate=False,
+    evaluation=True,
+    eval_freq=None,
+    eval_batches=None,
+    eval_num_samples=1,
+    kl_div_threshold=0.5,
+    loss_variant="grpo",
+    save_checkpoint=True,
+    rng=None,
+    sync_every=1,
+    vocab_chunk=None,
+):
+    """The GRPO training loop (reference grpo_engine.py:1014-1151).  Per epoch the reference model takes the policy's weights; per batch of
+    ``rlhf_grpo_prompt_collator`` prompts: every prompt ``num_samples`` times (``repeat_interleave``), rollouts with ``top_k=20, temp=1.0``
+    (``generate_batched_rollouts``), the masks (``batched_responses_collator``), the old and the reference log-probs and the reward model's scores without
+    gradients, ``z_scores``, then ``num_grad_updates`` updates of the policy on the GRPO loss of ``loss_variant``.  Every ``eval_freq`` steps
+    ``GRPOEvaluator.evaluate`` runs and, when ``CheckpointEvaluator.is_rlhf_grpo_best`` says so, the policy's ``state_dict`` is saved under
+    ``config.rlhf_grpo_checkpoint_dir``.  Returns None; ``policy_model`` is trained in place.
+
+    ``rng`` / ``sync_every`` go to the rollouts, ``vocab_chunk`` to the chunked head (module docstring)."""
+    reward_model.eval()
+    reference_model.eval()
+    chkp_eval = CheckpointEvaluator(kl_div_threshold=kl_div_threshold, beta=beta)
+    _build_lazy_buffers(policy_model, reference_model, reward_model)
+    hidden = _has_hidden_path(policy_model)
+
+    step = 0
+    for epoch in range(1, num_epoch + 1):
+        reference_model.load_state_dict(policy_model.state_dict())
+
+        for batch in train_loader:
+            step += 1
+            policy_model.eval()  # for every new batch the policy and the old policy are the same
+            dup_prompts = batch["padded_prompts"].repeat_interleave(num_samples, dim=0)
+            dup_prompts_masks = batch["prompt_masks"].repeat_interleave(num_samples, dim=0)
+            last_real_pos = batch["last_real_pos"].repeat_interleave(num_samples, dim=0)
+
+            responses = generate_batched_rollouts(
+                input_tensor=dup_prompts,
+                model=policy_model,
+                attention_mask=dup_prompts_masks,
+                max_gen=max_gen,
+                context_length=policy_config["context_length"],
+                top_k=20,
+                top_p=None,
+                min_p=None,
+                temp=1.0,
+                last_real=last_real_pos,
+                device=device,
+                rng=rng,
+                sync_every=sync_every,
+            )  # (batch_size * num_samples, max_prompt_len + generated): (B, S)
+            collated_batch = batched_responses_collator(responses, prompt_masks=dup_prompts_masks.to(device), device=device)
+            ids, attn_masks = collated_batch["padded_responses"], collated_batch["attn_masks"]
+            loss_mask = collated_batch["reward_masks"][:, 1:]  # the token positions the log-probs belong to
+
+            with torch.no_grad():
+                old_logprobs = _policy_label_log_probs(policy_model, ids, attn_masks, vocab_chunk)
+                reference_logprobs = _policy_label_log_probs(reference_model, ids, attn_masks, vocab_chunk)
+                rewards = reward_model(ids, attn_mask=attn_masks, reward_mask=collated_batch["reward_masks"])  # (B,)
+            advantages = z_scores(rewards.float(), num_samples, dr_grpo=loss_variant)
+
+            policy_model.train()
+            cum_grpo_loss = 0.0
+            for grad_step in range(num_grad_updates):
+                args = (ids, old_logprobs, reference_logprobs, advantages, loss_mask, num_samples, min_clip_eps, max_clip_eps, beta)
+                kwargs = dict(variant=loss_variant, unbiased_kl_estimate=unbiased_kl_estimate)
+                if hidden:
+                    grpo_loss_batch = grpo_policy_loss_from_hidden(policy_model.forward_hidden(ids, attn_masks), policy_model.out_head, *args,
+                                                                   vocab_chunk=vocab_chunk, **kwargs)
+                else:
+                    grpo_loss_batch = grpo_policy_loss(policy_model(ids, attn_masks), *args, **kwargs)
+                optimizer.zero_grad()
+                grpo_loss_batch.backward()
+                optimizer.step()
+                cum_grpo_loss += grpo_loss_batch.item()
+            avg_grpo_loss = cum_grpo_loss / num_grad_updates
+
+            if evaluation and eval_freq is not None and (step % eval_freq == 0):
+                eval_metrics = GRPOEvaluator.evaluate(
+                    train_loader=train_loader,
+                    val_loader=val_loader,
+                    policy_model=policy_model,
+                    reference_model=reference_model,
+                    evaluation_type="rlhf",
+                    reward_model=reward_model,
+                    policy_config=policy_config,
+                    device=device,
+                    max_gen=max_gen,
+                    eval_num_samples=eval_num_samples,
+                    eval_num_batches=eval_batches,
+                    rng=rng,
+                    sync_every=sync_every,
+                    vocab_chunk=vocab_chunk,
+                )
+                print(
+                    f"Step {step} | "
+                    f"Avg GRPO Loss: {avg_grpo_loss:.4f} | "
+                    f"T. Rwd: {eval_metrics['train_reward']:.4f}, T. KL Div: {eval_metrics['train_kl_div']:.4f} | "
+                    f"V. Rwd: {eval_metrics['val_reward']:.4f}, V. KL Div: {eval_metrics['val_kl_div']:.4f}"
+                )
+                if save_checkpoint and chkp_eval.is_rlhf_grpo_best(eval_metrics["val_kl_div"], eval_metrics["val_reward"]):
+                    os.makedirs(config.rlhf_grpo_checkpoint_dir, exist_ok=True)
+                    save_path = os.path.join(config.rlhf_grpo_checkpoint_dir, f"best_checkpoint_{step}_score_{chkp_eval.max_score_grpo:.3f}.pt")
+                    torch.save(policy_model.state_dict(), save_path)
+
+
+class GRPOEvaluator:
+    """The average reward and KL divergence of the policy on the training and the validation prompts, for RLHF (a reward model) and RLVR (the caller's
+    ``reward_calculator``)."""
+
+    @staticmethod
+    def _compute_grpo_metrics(
+        loader,
+        policy_model,
+        reference_model,
+        policy_config,
+        device,
+        max_gen,
+        eval_num_samples,
+        eval_num_batches,
+        evaluation_type="rlhf",
+        reward_model=None,
+        reward_calculator=None,
+        eos_ids=50256,
+        pad_id=50256,
+        sampling_params=None,
+        rng=None,
+        sync_every=1,
+        vocab_chunk=None,
+    ):
+        total_reward = 0.0
+        total_kl_div = 0.0
+        num_batches_to_eval = min(eval_num_batches, len(loader)) if eval_num_batches else len(loader)
+        for i, batch in enumerate(loader):
+            if i >= num_batches_to_eval:
+                break
+            dup_prompts = batch["padded_prompts"].repeat_interleave(eval_num_samples, dim=0)
+            dup_prompts_masks = batch["prompt_masks"].repeat_interleave(eval_num_samples, dim=0)
+            last_real_pos = batch["last_real_pos"].repeat_interleave(eval_num_samples, dim=0)
+            responses = generate_batched_rollouts(
+                input_tensor=dup_prompts,
+                model=policy_model,
+                attention_mask=dup_prompts_masks,
+                max_gen=max_gen,
+                context_length=policy_config["context_length"],
+                last_real=last_real_pos,
+                device=device,
+                eos_ids=eos_ids,
+                pad_id=pad_id,
+                rng=rng,
+                sync_every=sync_every,
+                **(sampling_params if sampling_params is not None else {}),
+            )
+            collated_batch = batched_responses_collator(responses, prompt_masks=dup_prompts_masks.to(device), device=device)
+            ids, attn_masks = collated_batch["padded_responses"], collated_batch["attn_masks"]
+            loss_mask = collated_batch["reward_masks"][:, 1:]
+            policy_logprobs = _policy_label_log_probs(policy_model, ids, attn_masks, vocab_chunk)
+            reference_logprobs = _policy_label_log_probs(reference_model, ids, attn_masks, vocab_chunk)
+            if evaluation_type == "rlhf":
+                rewards = reward_model(ids, attn_mask=attn_masks, reward_mask=collated_batch["reward_masks"])
+            elif evaluation_type == "rlvr":
+                correct_answers = [ans for ans in batch["answers"] for _ in range(eval_num_samples)]
+                rewards = reward_calculator(ids, correct_answers)
+            mean_batch_rewards = rewards.float().mean()
+            # the masked mean KL per sequence on the device (the k3 kernel, then the sequence average of kernels_pref), one read per batch
+            kl_div = kl_div_per_token(policy_logprobs, reference_logprobs)
+            seq_mask = torch.cat([torch.zeros_like(loss_mask[:, :1]), loss_mask], dim=1)  # the average takes the unshifted (B, T + 1) form
+            mean_kl_per_seq, den = KP.seq_logprob_fwd(kl_div, seq_mask)
+            mean_batch_kl_div = torch.where(den > 0, mean_kl_per_seq, torch.zeros_like(mean_kl_per_seq)).mean()  # upstream clamps an empty mask's count to 1: 0
+            total_reward += mean_batch_rewards.item()
+            total_kl_div += mean_batch_kl_div.item()
+        return {"reward": total_reward / num_batches_to_eval, "kl_div": total_kl_div / num_batches_to_eval}
+
+    @staticmethod
+    def evaluate(
+        train_loader,
+        val_loader,
+        policy_model,
+        reference_model,
+        policy_config,
+        device,
+        max_gen,
+        evaluation_type="rlhf",
+        reward_model=None,
+        reward_calculator=None,
+        eval_num_samples=1,
+        eval_num_batches=None,
+        eos_ids=50256,
+        pad_id=50256,
+        sampling_params=None,
+        rng=None,
+        sync_every=1,
+        vocab_chunk=None,
+    ):
+        """{"train_reward", "train_kl_div", "val_reward", "val_kl_div"} of the policy over ``eval_num_batches`` batches of each loader (None: all), with
+        ``eval_num_samples`` rollouts per prompt (``sampling_params``: top_k / top_p / min_p / temp of the rollouts, greedy by default), in eval mode and
+        without gradients; the policy is put back in train mode.  ``evaluation_type``: "rlhf" scores with ``reward_model``, "rlvr" calls
+        ``reward_calculator(padded_responses, correct_answers)`` with the batch's ``answers`` repeated per sample."""
+        if evaluation_type == "rlhf":
+            if reward_model is None:
+                raise ValueError("reward_model is required for RLHF evaluation")
+            reward_model.eval()
+        elif evaluation_type == "rlvr":
+            if reward_calculator is None:
+                raise ValueError("reward_calculator is required for RLVR evaluation")
+        else:
+            raise ValueError(f"Invalid evaluation type: {evaluation_type}")
+        policy_model.eval()
+        reference_model.eval()
+        _build_lazy_buffers(policy_model, reference_model, reward_model)
+        with torch.no_grad():  # upstream: inference_mode (see evaluate_reward_model)
+            metrics = [
+                GRPOEvaluator._compute_grpo_metrics(loader, policy_model, reference_model, policy_config, device, max_gen, eval_num_samples, eval_num_batches,
+                                                    evaluation_type=evaluation_type, reward_model=reward_model, reward_calculator=reward_calculator,
+                                                    eos_ids=eos_ids, pad_id=pad_id, sampling_params=sampling_params, rng=rng, sync_every=sync_every,
+                                                    vocab_chunk=vocab_chunk)
+                for loader in (train_loader, val_loader)
+            ]
+        policy_model.train()
+        return {"train_reward": metrics[0]["reward"], "train_kl_div": metrics[0]["kl_div"], "val_reward": metrics[1]["reward"],
+                "val_kl_div": metrics[1]["kl_div"]}
