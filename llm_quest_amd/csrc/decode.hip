@@ -3,7 +3,7 @@
 // linear layer a matrix-VECTOR product and attention one query row against the cache: both are HBM-bound byte streams (weights,
 // resp. cached K/V read exactly once per token), so the kernels here are bandwidth kernels, not MFMA kernels.
 //   gemv            y[m, :] = x[m, :] W^T (+ residual), m < 8 rows: one wave per output column, 16-byte weight loads, fp32 accumulate
-//   attn_decode     one query per (batch, head) over `len` cached keys: 4 waves split the keys (flash-decoding), scores with the
+//   attn_decode     one query per (batch, head) over `len` cached keys: 8 waves split the keys (flash-decoding), scores with the
 //                   key on the lane, P V with the feature on the lane, combined through LDS; reference mask semantics (finite fill)
 //   gemv_pro        the same weight stream with the row operation that feeds it folded in (PRO 1: RMSNorm of x, PRO 2: SwiGLU of a gate-up row): every
 //                   workgroup rebuilds the <= 8 operand rows in LDS (a few KB) instead of a launch of its own writing them -- a decode step is launch-bound
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void gemv_pro_kernel(int M, int64_t N, int K, 
 }
 
 // ------------------------------------------------------------------------------------------- decode attention
-// grid (Hq, B), WAVES waves; chunks of CK keys go round the waves (chunk c to wave c % WAVES).  D = 32 .. 256.
+// grid (Hq, B), WAVES waves; chunks of CK keys go round the splits and the waves (chunk c to split c % S, there to wave (c / S) % WAVES).  D = 32 .. 256.
 // POST: the launch starts from the fused QKV stream's raw row instead of finished q rows and a finished cache row -- QK-RMSNorm + RoPE of this head's query (to LDS, never to
 // memory) and of its kv head's new key, which goes with the value head into cache row *write_pos, exactly as qknorm_rope_fwd_kernel (norm_rope.hip) computes them: fp32 norm
 // rounded to bf16, bf16-rounded cos / sin, every product rounded.  The query heads of one kv head all write the same bytes to the same row; each workgroup reads back its own.
@@ -473,6 +473,9 @@ __global__ __launch_bounds__(256) void argmax_part_kernel(int64_t V, const bf16_
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; ++w) argmax_merge(best, idx, bv[w], bi[w]);
+        // no element of the range compared greater than -inf (all -inf, or NaN: a NaN never compares greater): the range answers with its first column, so a row of
+        // nothing else returns 0 as torch.argmax does on -inf, and the index is always one of the row; a range without columns keeps the sentinel and loses every tie
+        if (idx == 0x7fffffffffffffffll && c0 < V) idx = c0;
         pv[(int64_t)blockIdx.y * ARG_SPLIT + blockIdx.x] = best;
         pi[(int64_t)blockIdx.y * ARG_SPLIT + blockIdx.x] = idx;
     }
