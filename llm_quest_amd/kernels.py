@@ -440,7 +440,11 @@ def rmsnorm_fwd(x2d, w, eps=1e-6, want_rstd=True):
 def rmsnorm_bwd(x2d, w, rstd, dy, dres=None, dw_out=None, dw_accumulate=False):
     """Returns (dx [+ dres], dw).  dw goes to ``dw_out`` (bf16/fp32, optionally accumulated) or a new fp32 tensor."""
     L.require_gpu(x2d, w, rstd, dy, dres)
+    if x2d.dim() != 2 or x2d.dtype != BF16 or w.dtype != BF16 or not x2d.is_contiguous() or w.numel() != x2d.shape[1]:
+        raise ValueError("rmsnorm_bwd: x must be contiguous bf16 [rows,width], w bf16 [width]")
     rows, width = x2d.shape
+    if not (rstd.dtype == F32 and rstd.is_contiguous() and rstd.numel() == rows):
+        raise ValueError("rmsnorm_bwd: rstd must be contiguous fp32 [rows]")
     if not (dy.is_contiguous() and dy.shape == x2d.shape and dy.dtype == BF16):
         raise ValueError("rmsnorm_bwd: dy must be contiguous bf16 like x")
     if dres is not None and not (dres.is_contiguous() and dres.shape == x2d.shape and dres.dtype == BF16):
@@ -504,6 +508,8 @@ def swiglu_fwd(gu, F):
 
 def swiglu_bwd(gu, da, F):
     L.require_gpu(gu, da)
+    if not (gu.dim() == 2 and gu.is_contiguous() and gu.dtype == BF16 and gu.shape[1] == 2 * F):
+        raise ValueError("swiglu_bwd: gu must be contiguous bf16 [tokens,2F]")
     if not (da.is_contiguous() and da.dtype == BF16 and tuple(da.shape) == (gu.shape[0], F)):
         raise ValueError("swiglu_bwd: da must be contiguous bf16 [tokens,F]")
     dgu = torch.empty_like(gu)
@@ -949,6 +955,8 @@ def gelu_fwd(x, tanh=False):
 
 def gelu_bwd(x, dy, tanh=False):
     L.require_gpu(x, dy)
+    if x.dtype != BF16 or not x.is_contiguous() or x.numel() % 8:
+        raise ValueError("gelu_bwd: x must be contiguous bf16 with numel % 8 == 0")
     if dy.dtype != BF16 or not dy.is_contiguous() or dy.shape != x.shape:
         raise ValueError("gelu_bwd: dy must be contiguous bf16 like x")
     dx = torch.empty_like(x)
@@ -958,10 +966,15 @@ def gelu_bwd(x, dy, tanh=False):
 
 def layernorm_bwd(x2d, scale, mean, rsig, dy, dres=None, eps=1e-5, dscale_out=None, dshift_out=None, accumulate=False, mode=0):
     """Returns dx fp32 (+ dres).  dscale/dshift go to the given fp32 destinations (optionally accumulated) or new tensors."""
-    L.require_gpu(x2d, dy, dres)
+    L.require_gpu(x2d, scale, mean, rsig, dy, dres)
     rows, width = x2d.shape
     if x2d.dtype != F32 or not x2d.is_contiguous() or not dy.is_contiguous() or dy.shape != x2d.shape:
         raise ValueError("layernorm_bwd: x fp32 contiguous, dy contiguous of the same shape")
+    if scale.dtype != F32 or scale.numel() != width or not scale.is_contiguous():
+        raise ValueError("layernorm_bwd: scale must be contiguous fp32 [width]")
+    for t, name in ((mean, "mean"), (rsig, "rsig")):
+        if t.dtype != F32 or not t.is_contiguous() or t.numel() != rows:
+            raise ValueError(f"layernorm_bwd: {name} must be contiguous fp32 [rows]")
     if dres is not None and (dres.dtype != F32 or not dres.is_contiguous() or dres.shape != x2d.shape):
         raise ValueError("layernorm_bwd: dres must be contiguous fp32 like x")
     dx = torch.empty_like(x2d)
