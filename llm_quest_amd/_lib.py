@@ -179,6 +179,11 @@ SIGNATURES = {
     # Rollout sampling: temperature / top-k / top-p / min-p rows with the rollout's per-token bookkeeping, the response masks (csrc/sampling.hip)
     "mi355_sample_rows": [_L, _L, _P, _I, _L, _I, _I, _F, _F, _F, _P, _U, _U, _P, _P, _P, _I, _L, _P, _L, _P, _L, _L, _P, _P],
     "mi355_response_masks": [_L, _L, _L, _P, _L, _P, _L, _P, _I, _L, _P, _P, _P],
+    # Llama 3.2 and QK-Clip: RoPE on the packed projection, the per-head maximum attention logit, the in-place weight clip (csrc/llama3.hip)
+    "mi355_llama_rope_fwd": [_L, _I, _I, _I, _P, _L, _P, _P, _L, _P, _P, _P, _P],
+    "mi355_llama_rope_bwd": [_L, _I, _I, _I, _P, _L, _P, _L, _P, _P, _L, _P, _P, _L, _P],
+    "mi355_attn_max_logit": [_I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _F, _P, _L, _P, _P],
+    "mi355_qk_clip": [_I, _I, _I, _L, _P, _P, _P, _F, _F, _I, _P],
 }
 # size / constant queries: no stream argument, the return value is the answer (name -> (argtypes, restype))
 QUERIES = {
@@ -191,6 +196,7 @@ QUERIES = {
     "mi355_hc_width_bwd_partial_width": ([_I, _I], _L),
     "mi355_moe_row_align": ([], _I),
     "mi355_moe_plan_workspace_bytes": ([_L, _I, _I], _L),
+    "mi355_attn_max_logit_partials": ([_I, _I, _I], _L),
 }
 
 _lib = None
