@@ -116,7 +116,7 @@ SIGNATURES = {
     "mi355_hc_width_bwd": [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "mi355_hc_stream_sum": [_L, _I, _I, _P, _P, _P],
     "mi355_hc_stream_broadcast": [_L, _I, _I, _P, _P, _P],
-    # Gemma3: sliding-window attention and its row kernels (csrc/gemma3.hip)
+    # Gemma3: sliding-window attention (csrc/attention_band.hip, the banded family at DV = D without a sink) and its row kernels (csrc/gemma3.hip)
     "mi355_swa_attn_fwd": [_I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _F, _P],
     "mi355_swa_attn_bwd": [_I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _L, _P, _L, _P, _L, _F, _P],
     "mi355_g3_rmsnorm_fwd": [_L, _I, _P, _P, _P, _P, _F, _P],
@@ -155,7 +155,7 @@ SIGNATURES = {
     "mi355_cmoe_loss": [_L, _P, _F, _P, _P, _P],
     "mi355_cmoe_bias_act_fwd": [_L, _I, _I, _P, _P, _P, _L, _P, _L, _P, _L, _P, _L, _I, _P],
     "mi355_cmoe_segment_colsum": [_L, _I, _I, _P, _P, _P, _L, _P, _I, _P, _L, _I, _I, _P],
-    # MiMo-V2-Flash: attention with a sink and its own v head dim, the sink gradient, per-head RMSNorm + partial RoPE (csrc/mimo.hip)
+    # MiMo-V2-Flash: attention with a sink and its own v head dim, the sink gradient (csrc/attention_band.hip, the banded family); per-head RMSNorm + partial RoPE (csrc/mimo.hip)
     "mi355_sink_attn_fwd": [_I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _P, _L, _P, _F, _P],
     "mi355_sink_attn_bwd": [_I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P, _L, _P, _L, _P, _I, _F, _P],
     "mi355_mimo_normrope_fwd": [_L, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _L, _P, _L, _F, _P],

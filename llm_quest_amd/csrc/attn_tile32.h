@@ -1,7 +1,8 @@
-// The plain 32-key tile layer of attention_generic.hip and gemma3.hip: padded, unswizzled LDS images of 32 rows x D bf16, the MFMA operand
-// fragments read from them (mfma_f32_32x32x16_bf16, the transposed one through ds_read_b64_tr_b16), the write-out of a transposed accumulator,
-// and the delta kernel of the backward.  Not the layer of attention.hip: attn_common.h has its own swizzled, DMA-fed frag_rows / frag_cols /
-// pack_frag under the same names, so a translation unit includes one of the two headers, never both.
+// The plain 32-key tile layer of attention_generic.hip, attention_band.hip, deepseek.hip and llama3.hip's max-logit kernel: padded, unswizzled
+// LDS images of 32 rows x D bf16, the MFMA operand fragments read from them (mfma_f32_32x32x16_bf16, the transposed one through
+// ds_read_b64_tr_b16), the steps of one tile (score product, online-softmax update, transposed accumulate), the write-out of a transposed
+// accumulator, and the delta kernel of the backward.  Not the layer of attention.hip: attn_common.h has its own swizzled, DMA-fed frag_rows /
+// frag_cols / pack_frag under the same names, so a translation unit includes one of the two headers, never both.
 #pragma once
 #include "common.h"
 
@@ -63,6 +64,55 @@ __device__ __forceinline__ void load_row_frags(const bf16_t* rowptr, bool valid,
         f[ks] = __builtin_bit_cast(bf16x8, v);
     }
 }
+
+// ---- the steps of one 32-key tile, as every kernel on this layer takes them.  Each family keeps its own mask, tile range and write-out.
+// the image row (key of a score tile S^T, query in the key-major pass) that element i of a lane's accumulator tile belongs to
+__device__ __forceinline__ int acc_row(int i, int lane) { return 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3); }
+__device__ __forceinline__ void zero_tile(f32x16& t) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t[i] = 0.f;
+}
+template <int N>
+__device__ __forceinline__ void zero_tiles(f32x16 (&t)[N]) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) zero_tile(t[n]);
+}
+// t += (32 image rows x D) . (the D features of the row held on the lane): a score tile S^T = K Q^T, or dP^T = V dO^T
+template <int D>
+__device__ __forceinline__ void mma_rows(f32x16& t, const char* img, const bf16x8 (&f)[Tile32<D>::KS], int lane) {
+#pragma unroll
+    for (int ks = 0; ks < Tile32<D>::KS; ++ks) t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(img, ks, lane), f[ks], t, 0, 0, 0);
+}
+// t += (image columns c0 .. c0+31 of a D-wide image)^T . P^T, P^T packed from an accumulator tile as p0 = pack_frag(., 0), p1 = pack_frag(., 1)
+template <int D>
+__device__ __forceinline__ void mma_cols(f32x16& t, const char* img, int c0, const bf16x8& p0, const bf16x8& p1, int lane) {
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(img, c0, 0, lane), p0, t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(img, c0, 16, lane), p1, t, 0, 0, 0);
+}
+// The online-softmax update of a row's state (m, l, acc) with one tile of masked scores (log2 units, NEG_INF where masked) and mx, the largest
+// of the lane's 16 (the caller's mask loop keeps it): s becomes exp2(s - m).  m_use: a row no tile has reached yet (a window that starts
+// later, a row past S) keeps m = -inf and adds nothing.
+template <int N>
+__device__ __forceinline__ void online_softmax(f32x16& s, float mx, float& m, float& l, f32x16 (&acc)[N]) {
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m, mx);
+    const float m_use = m_new == NEG_INF ? 0.f : m_new;
+    const float alpha = exp2f(m - m_use);
+    float rs = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        s[i] = exp2f(s[i] - m_use);
+        rs += s[i];
+    }
+    rs += __shfl_xor(rs, 32, 64);
+    l = l * alpha + rs;
+    m = m_new;
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[n][i] *= alpha;
+}
+
 // accumulator tile [32 d x 32 rows-on-lane] -> token-major bf16 rows (4 consecutive d per 8-byte store)
 template <int NDT>
 __device__ __forceinline__ void store_t_tiles(const f32x16 (&acc)[NDT], float mul, bf16_t* rowptr, bool valid, int lane) {

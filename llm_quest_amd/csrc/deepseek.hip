@@ -4,7 +4,7 @@
 // expand()ed to every head):
 //   s(i, j) = scale * (q_nope_i . k_nope_j + q_rope_i . k_rope_j),  j <= i;  o_i = softmax_j(s) v_j
 // The score contraction is DK = Dn + Dr wide, the value / context contraction Dn; k_rope is ONE Dr-wide row per token shared by all heads.
-// Same data flow as attention_generic.hip / gemma3.hip -- S^T = K Q^T with the query on the MFMA lane (mfma_f32_32x32x16_bf16), lane-local online
+// Same data flow as attention_generic.hip / attention_band.hip -- S^T = K Q^T with the query on the MFMA lane (mfma_f32_32x32x16_bf16), lane-local online
 // softmax in fp32, P^T packed from the accumulators as the B operand of O^T += V^T P^T, plain padded LDS images, one 32-key tile per barrier pair,
 // no pipelining; backward with delta = rowsum(dO * O), a query-major dQ pass and a key-major dK/dV pass, no atomics.  What differs: the K image
 // (32 x DK) is composed in LDS from two sources, the head's k_nope columns and the shared k_rope columns, the V image is Dn wide, nothing is
@@ -31,6 +31,8 @@
 // as 144 / 272 do for the 64- / 128-wide V image, so the ds_read_b128 of frag_rows stays conflict-free; the ds_read_b64_tr_b16 of frag_cols reads
 // the images exactly as the generic and sliding-window kernels do.
 #include <initializer_list>
+
+#include "host_checks.h"
 
 #include "attn_tile32.h"
 #include "rows_bf16.h"
@@ -102,10 +104,7 @@ __global__ __launch_bounds__(256) void mla_fwd_kernel(int S, int Hq, const bf16_
     bf16x8 qf[CK::KS];
     load_cat_frags<DN, DR>(qn + (tok0 + query) * ldqn + (int64_t)h * DN, qr + (tok0 + query) * ldqr + (int64_t)h * DR, qvalid, lane, qf);
     f32x16 acc[CV::DT];
-#pragma unroll
-    for (int dt = 0; dt < CV::DT; ++dt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[dt][i] = 0.f;
+    zero_tiles(acc);
     float m = NEG_INF, l = 0.f;
     const int qlast = (qb + 127 < S ? qb + 127 : S - 1);
     for (int kt = 0; kt <= qlast / 32; ++kt) {
@@ -117,41 +116,20 @@ __global__ __launch_bounds__(256) void mla_fwd_kernel(int S, int Hq, const bf16_
         __syncthreads();
         if (q0 >= S || key0 > q0 + 31) continue;  // tile above this wave's diagonal
         f32x16 s;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s[i] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < CK::KS; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<DK>(kimg, ks, lane), qf[ks], s, 0, 0, 0);
+        zero_tile(s);
+        mma_rows<DK>(s, kimg, qf, lane);
         float mx = NEG_INF;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int key = key0 + 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3);
+            const int key = key0 + acc_row(i, lane);
             const bool ok = key < S && key <= query;
             s[i] = ok ? s[i] * scale_log2 : NEG_INF;
             mx = fmaxf(mx, s[i]);
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m, mx);
-        const float m_use = m_new == NEG_INF ? 0.f : m_new;  // only the rows past S of a ragged last wave: never stored
-        const float alpha = exp2f(m - m_use);
-        float rs = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            s[i] = exp2f(s[i] - m_use);
-            rs += s[i];
-        }
-        rs += __shfl_xor(rs, 32, 64);
-        l = l * alpha + rs;
-        m = m_new;
-#pragma unroll
-        for (int dt = 0; dt < CV::DT; ++dt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[dt][i] *= alpha;
+        online_softmax(s, mx, m, l, acc);
         const bf16x8 p0 = pack_frag(s, 0), p1 = pack_frag(s, 1);
 #pragma unroll
-        for (int dt = 0; dt < CV::DT; ++dt) {
-            acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<DN>(vimg, 32 * dt, 0, lane), p0, acc[dt], 0, 0, 0);
-            acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<DN>(vimg, 32 * dt, 16, lane), p1, acc[dt], 0, 0, 0);
-        }
+        for (int dt = 0; dt < CV::DT; ++dt) mma_cols<DN>(acc[dt], vimg, 32 * dt, p0, p1, lane);
     }
     store_t_tiles<CV::DT>(acc, 1.f / l, o + (tok0 + query) * ldo + (int64_t)h * DN, qvalid, lane);
     if (lane < 32 && qvalid) lse[((int64_t)b * Hq + h) * S + query] = (m + log2f(l)) * LN2;
@@ -184,10 +162,7 @@ __global__ __launch_bounds__(256) void mla_bwd_dq_kernel(int S, int Hq, const bf
     const float delta_q = qvalid ? delta[((int64_t)b * Hq + h) * S + query] : 0.f;
     const float scale_log2 = scale * LOG2E;
     f32x16 acc[CK::DT];
-#pragma unroll
-    for (int dt = 0; dt < CK::DT; ++dt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[dt][i] = 0.f;
+    zero_tiles(acc);
     const int qlast = (qb + 127 < S ? qb + 127 : S - 1);
     for (int kt = 0; kt <= qlast / 32; ++kt) {
         const int key0 = kt * 32;
@@ -198,25 +173,20 @@ __global__ __launch_bounds__(256) void mla_bwd_dq_kernel(int S, int Hq, const bf
         __syncthreads();
         if (q0 >= S || key0 > q0 + 31) continue;
         f32x16 s, dp;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < CK::KS; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<DK>(kimg, ks, lane), qf[ks], s, 0, 0, 0);
-#pragma unroll
-        for (int ks = 0; ks < CV::KS; ++ks) dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<DN>(vimg, ks, lane), gf[ks], dp, 0, 0, 0);
+        zero_tile(s);
+        zero_tile(dp);
+        mma_rows<DK>(s, kimg, qf, lane);
+        mma_rows<DN>(dp, vimg, gf, lane);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int key = key0 + 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3);
+            const int key = key0 + acc_row(i, lane);
             const bool ok = qvalid && key <= query;
             const float p = ok ? exp2f(s[i] * scale_log2 - lse_q) : 0.f;
             s[i] = p * (dp[i] - delta_q) * scale;
         }
         const bf16x8 d0 = pack_frag(s, 0), d1 = pack_frag(s, 1);
 #pragma unroll
-        for (int dt = 0; dt < CK::DT; ++dt) {
-            acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<DK>(kimg, 32 * dt, 0, lane), d0, acc[dt], 0, 0, 0);
-            acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<DK>(kimg, 32 * dt, 16, lane), d1, acc[dt], 0, 0, 0);
-        }
+        for (int dt = 0; dt < CK::DT; ++dt) mma_cols<DK>(acc[dt], kimg, 32 * dt, d0, d1, lane);
     }
     bf16_t* on = dqn + (tok0 + query) * lddqn + (int64_t)h * DN;
     bf16_t* orp = dqr + (tok0 + query) * lddqr + (int64_t)h * DR;
@@ -256,14 +226,8 @@ __global__ __launch_bounds__(256) void mla_bwd_dkv_kernel(int S, int Hq, const b
     load_row_frags<DN>(v + (tok0 + key) * ldv + (int64_t)h * DN, kvalid, lane, vf);
     const float scale_log2 = scale * LOG2E;
     f32x16 adk[NK], adv[NV];
-#pragma unroll
-    for (int dt = 0; dt < NK; ++dt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) adk[dt][i] = 0.f;
-#pragma unroll
-    for (int dt = 0; dt < NV; ++dt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) adv[dt][i] = 0.f;
+    zero_tiles(adk);
+    zero_tiles(adv);
     for (int qt = kb / 32; qt <= (S - 1) / 32; ++qt) {
         const int qs = qt * 32;
         __syncthreads();
@@ -278,15 +242,13 @@ __global__ __launch_bounds__(256) void mla_bwd_dkv_kernel(int S, int Hq, const b
         __syncthreads();
         if (k0 >= S || qs + 31 < k0) continue;  // every query of the tile precedes this wave's keys
         f32x16 s, dp;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < CK::KS; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<DK>(qimg, ks, lane), kf[ks], s, 0, 0, 0);
-#pragma unroll
-        for (int ks = 0; ks < CV::KS; ++ks) dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<DN>(gimg, ks, lane), vf[ks], dp, 0, 0, 0);
+        zero_tile(s);
+        zero_tile(dp);
+        mma_rows<DK>(s, qimg, kf, lane);
+        mma_rows<DN>(dp, gimg, vf, lane);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int r = 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3);
+            const int r = acc_row(i, lane);
             const int qi = qs + r;
             const bool ok = kvalid && qi < S && key <= qi;
             const float p = ok ? exp2f(s[i] * scale_log2 - stat[0][r]) : 0.f;
@@ -297,14 +259,12 @@ __global__ __launch_bounds__(256) void mla_bwd_dkv_kernel(int S, int Hq, const b
 #pragma unroll
         for (int dt = 0; dt < NV; ++dt) {
             const int c0 = 32 * (slice * NV + dt);
-            adv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<DN>(gimg, c0, 0, lane), p0, adv[dt], 0, 0, 0);
-            adv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<DN>(gimg, c0, 16, lane), p1, adv[dt], 0, 0, 0);
+            mma_cols<DN>(adv[dt], gimg, c0, p0, p1, lane);
         }
 #pragma unroll
         for (int dt = 0; dt < NK; ++dt) {
             const int c0 = 32 * (slice * NK + dt);
-            adk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<DK>(qimg, c0, 0, lane), d0, adk[dt], 0, 0, 0);
-            adk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<DK>(qimg, c0, 16, lane), d1, adk[dt], 0, 0, 0);
+            mma_cols<DK>(adk[dt], qimg, c0, d0, d1, lane);
         }
     }
     bf16_t* okn = dkn + (tok0 + key) * lddkn + (int64_t)h * DN;
@@ -368,13 +328,6 @@ __global__ __launch_bounds__(256) void mla_rope_kernel(int64_t tokens, int S, in
     }
 }
 
-// the kernels move 16 bytes at a time: every operand pointer must be 16-byte aligned (NULL passes here and is refused by the null check)
-bool aligned16(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if ((uintptr_t)p & 15) return false;
-    return true;
-}
-
 bool lds_ok(std::initializer_list<int64_t> lds, int64_t least) {
     for (int64_t ld : lds)
         if (ld < least || ld % 8) return false;
@@ -389,7 +342,9 @@ int check_mla(const char* who, int B, int S, int Hq, int Dn, int Dr) {
     return 0;
 }
 
-inline int row_grid(int64_t groups) {
+// Not host_checks.h's row_grid: this one counts groups of 128 / Dr rows (what a wave of mla_rope_kernel covers per trip) and caps the grid at 4096
+// workgroups where row_grid caps at 2048.  Merging the two would change the launch grids of mi355_mla_rope_*.
+inline int group_grid(int64_t groups) {
     int64_t g = (groups + 3) / 4;
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
@@ -470,7 +425,7 @@ extern "C" int mi355_mla_rope_fwd(int64_t tokens, int S, int Hq, int Dr, const v
     MI355_REQUIRE(ldq >= (int64_t)Hq * Dr && ldqo >= (int64_t)Hq * Dr && ldk >= Dr && ldko >= Dr,
                   "mi355_mla_rope_fwd: a leading dimension is smaller than its row (Hq*Dr, Dr)");
     MI355_REQUIRE(q_rope_pre && k_rope_pre && cos_t && sin_t && q_rope && k_rope, "mi355_mla_rope_fwd: null pointer");
-    const int grid = row_grid(tokens * (Hq + 1) / (128 / Dr) + 1);
+    const int grid = group_grid(tokens * (Hq + 1) / (128 / Dr) + 1);
     if (Dr == 32)
         mla_rope_kernel<32, false><<<grid, 256, 0, ST(stream)>>>(tokens, S, Hq, BF(q_rope_pre), ldq, BF(k_rope_pre), ldk, nullptr, cos_t, sin_t,
                                                                  (bf16_t*)q_rope, ldqo, (bf16_t*)k_rope, ldko);
@@ -488,7 +443,7 @@ extern "C" int mi355_mla_rope_bwd(int64_t tokens, int S, int Hq, int Dr, const v
     MI355_REQUIRE(lddq >= (int64_t)Hq * Dr && lddqp >= (int64_t)Hq * Dr && lddkp >= Dr,
                   "mi355_mla_rope_bwd: a leading dimension is smaller than its row (Hq*Dr, Dr)");
     MI355_REQUIRE(dq_rope && dk_rope_heads && cos_t && sin_t && dq_rope_pre && dk_rope_pre, "mi355_mla_rope_bwd: null pointer");
-    const int grid = row_grid(tokens * (Hq + 1) / (128 / Dr) + 1);
+    const int grid = group_grid(tokens * (Hq + 1) / (128 / Dr) + 1);
     if (Dr == 32)
         mla_rope_kernel<32, true><<<grid, 256, 0, ST(stream)>>>(tokens, S, Hq, BF(dq_rope), lddq, nullptr, 0, dk_rope_heads, cos_t, sin_t,
                                                                 (bf16_t*)dq_rope_pre, lddqp, (bf16_t*)dk_rope_pre, lddkp);

@@ -1,14 +1,5 @@
-// Gemma3 (reference llama3_to_gemma3/): sliding-window causal attention and the three row kernels the family needs beside what exists.
-//
-// Sliding-window attention (gemma3_attention.py:49-128, where it is a [b, h, s, w, d] gather of key / value windows):
-//   allowed(i, j) = i - W < j <= i,  W >= 1;  softmax over the allowed keys of scale * q_i . k_j;  W >= S is plain causal attention.
-// Same data flow as attention_generic.hip -- S^T = K Q^T with the query on the MFMA lane (mfma_f32_32x32x16_bf16), lane-local online softmax,
-// P^T packed from the accumulators as the B operand of O^T += V^T P^T, plain padded LDS images, one 32-key tile per barrier pair, no
-// pipelining; backward with delta = rowsum(dO * O), a query-major dQ pass and a key-major dK/dV pass, no atomics -- and one difference, which
-// is the point: only the key tiles that meet the band are walked.  A workgroup of 128 queries starting at qb visits keys
-// max(0, qb - W + 1) .. q_last; a workgroup of 128 keys [kb, k_last] visits queries kb .. min(S - 1, k_last + W - 1); inside it a wave skips
-// the tiles outside its own 32 rows' band.  No row is ever fully masked (j = i is always allowed).  The host clamps W to S, so every W >= S runs
-// the same instructions on the same numbers.
+// Gemma3 (reference llama3_to_gemma3/): the three row kernels the family needs beside what exists.  Its sliding-window attention
+// (mi355_swa_attn_fwd / _bwd) is the banded family of attention_band.hip, called with DV = D and no sink.
 //
 // Row kernels (one wave per row, fp32 math, one rounding at the output; parameter gradients as per-workgroup partial rows for
 // mi355_reduce_rows_f32):
@@ -16,253 +7,10 @@
 //   RoPE + per-head LayerNorm (gemma3_attention.py:203-207, 13-43): half-split rotation with bf16-rounded cos / sin, then
 //     (r - mean) / (std + eps) * scale + shift over head_dim, population std; one scale / shift pair for the query heads, one for the key heads.
 //   GeGLU (gemma3_transformer_block.py:101-106): a = lin1 * gelu_erf(lin_gate) on the fused [T, 2F] projection.
-#include <initializer_list>
-
-#include "attn_tile32.h"
+#include "host_checks.h"
 #include "rows_bf16.h"
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------ sliding-window attention, forward
-// W is already clamped to [1, S] and S <= 2^30 - 64 (check_swa): every sum of an index and W below stays inside int.
-template <int D>
-__global__ __launch_bounds__(256) void swa_fwd_kernel(int S, int Hq, int Hkv, int W, const bf16_t* __restrict__ q, int64_t ldq,
-                                                      const bf16_t* __restrict__ k, int64_t ldk, const bf16_t* __restrict__ v, int64_t ldv,
-                                                      bf16_t* __restrict__ o, int64_t ldo, float* __restrict__ lse, float scale_log2) {
-    using C = Tile32<D>;
-    __shared__ __attribute__((aligned(16))) char smem[2 * C::IMG];
-    char* kimg = smem;
-    char* vimg = smem + C::IMG;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.z, h = blockIdx.y, hkv = h / (Hq / Hkv);
-    const int qb = blockIdx.x * 128;
-    const int q0 = qb + wave * 32;
-    const int query = q0 + (lane & 31);
-    const bool qvalid = query < S;
-    const int64_t tok0 = (int64_t)b * S;
-    bf16x8 qf[C::KS];
-    load_row_frags<D>(q + (tok0 + query) * ldq + (int64_t)h * D, qvalid, lane, qf);
-    f32x16 acc[C::DT];
-#pragma unroll
-    for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[dt][i] = 0.f;
-    float m = NEG_INF, l = 0.f;
-    const int qlast = (qb + 127 < S ? qb + 127 : S - 1);
-    const int kfirst = qb - W + 1 > 0 ? qb - W + 1 : 0;  // first key of the workgroup's first query's window
-    for (int kt = kfirst / 32; kt <= qlast / 32; ++kt) {
-        const int key0 = kt * 32;
-        __syncthreads();
-        load_tile<D, 256>(kimg, k + (tok0 + key0) * ldk + (int64_t)hkv * D, ldk, S - key0, threadIdx.x);
-        load_tile<D, 256>(vimg, v + (tok0 + key0) * ldv + (int64_t)hkv * D, ldv, S - key0, threadIdx.x);
-        __syncthreads();
-        // tile above this wave's diagonal, or wholly before the window of its first query (later queries' windows start later still)
-        if (q0 >= S || key0 > q0 + 31 || key0 + 31 + W <= q0) continue;
-        f32x16 s;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s[i] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < C::KS; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(kimg, ks, lane), qf[ks], s, 0, 0, 0);
-        float mx = NEG_INF;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int key = key0 + 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3);
-            const bool ok = key < S && key <= query && key + W > query;
-            s[i] = ok ? s[i] * scale_log2 : NEG_INF;
-            mx = fmaxf(mx, s[i]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m, mx);
-        const float m_use = m_new == NEG_INF ? 0.f : m_new;  // a row whose window this tile does not reach yet
-        const float alpha = exp2f(m - m_use);
-        float rs = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            s[i] = exp2f(s[i] - m_use);
-            rs += s[i];
-        }
-        rs += __shfl_xor(rs, 32, 64);
-        l = l * alpha + rs;
-        m = m_new;
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[dt][i] *= alpha;
-        const bf16x8 p0 = pack_frag(s, 0), p1 = pack_frag(s, 1);
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt) {
-            acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(vimg, 32 * dt, 0, lane), p0, acc[dt], 0, 0, 0);
-            acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(vimg, 32 * dt, 16, lane), p1, acc[dt], 0, 0, 0);
-        }
-    }
-    store_t_tiles<C::DT>(acc, 1.f / l, o + (tok0 + query) * ldo + (int64_t)h * D, qvalid, lane);
-    if (lane < 32 && qvalid) lse[((int64_t)b * Hq + h) * S + query] = (m + log2f(l)) * LN2;
-}
-
-// ------------------------------------------------------------------------------------------------ dQ pass (query-major, the forward's band)
-template <int D>
-__global__ __launch_bounds__(256) void swa_bwd_dq_kernel(int S, int Hq, int Hkv, int W, const bf16_t* __restrict__ q, int64_t ldq,
-                                                         const bf16_t* __restrict__ k, int64_t ldk, const bf16_t* __restrict__ v, int64_t ldv,
-                                                         const bf16_t* __restrict__ d_o, int64_t lddo, const float* __restrict__ lse,
-                                                         const float* __restrict__ delta, bf16_t* __restrict__ dq, int64_t lddq, float scale) {
-    using C = Tile32<D>;
-    __shared__ __attribute__((aligned(16))) char smem[2 * C::IMG];
-    char* kimg = smem;
-    char* vimg = smem + C::IMG;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.z, h = blockIdx.y, hkv = h / (Hq / Hkv);
-    const int qb = blockIdx.x * 128;
-    const int q0 = qb + wave * 32;
-    const int query = q0 + (lane & 31);
-    const bool qvalid = query < S;
-    const int64_t tok0 = (int64_t)b * S;
-    bf16x8 qf[C::KS], gf[C::KS];
-    load_row_frags<D>(q + (tok0 + query) * ldq + (int64_t)h * D, qvalid, lane, qf);
-    load_row_frags<D>(d_o + (tok0 + query) * lddo + (int64_t)h * D, qvalid, lane, gf);
-    const float lse_q = qvalid ? lse[((int64_t)b * Hq + h) * S + query] * LOG2E : 0.f;
-    const float delta_q = qvalid ? delta[((int64_t)b * Hq + h) * S + query] : 0.f;
-    const float scale_log2 = scale * LOG2E;
-    f32x16 acc[C::DT];
-#pragma unroll
-    for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[dt][i] = 0.f;
-    const int qlast = (qb + 127 < S ? qb + 127 : S - 1);
-    const int kfirst = qb - W + 1 > 0 ? qb - W + 1 : 0;
-    for (int kt = kfirst / 32; kt <= qlast / 32; ++kt) {
-        const int key0 = kt * 32;
-        __syncthreads();
-        load_tile<D, 256>(kimg, k + (tok0 + key0) * ldk + (int64_t)hkv * D, ldk, S - key0, threadIdx.x);
-        load_tile<D, 256>(vimg, v + (tok0 + key0) * ldv + (int64_t)hkv * D, ldv, S - key0, threadIdx.x);
-        __syncthreads();
-        if (q0 >= S || key0 > q0 + 31 || key0 + 31 + W <= q0) continue;
-        f32x16 s, dp;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < C::KS; ++ks) {
-            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(kimg, ks, lane), qf[ks], s, 0, 0, 0);
-            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(vimg, ks, lane), gf[ks], dp, 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int key = key0 + 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3);
-            const bool ok = qvalid && key <= query && key + W > query;
-            const float p = ok ? exp2f(s[i] * scale_log2 - lse_q) : 0.f;
-            s[i] = p * (dp[i] - delta_q) * scale;
-        }
-        const bf16x8 d0 = pack_frag(s, 0), d1 = pack_frag(s, 1);
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt) {
-            acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(kimg, 32 * dt, 0, lane), d0, acc[dt], 0, 0, 0);
-            acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(kimg, 32 * dt, 16, lane), d1, acc[dt], 0, 0, 0);
-        }
-    }
-    store_t_tiles<C::DT>(acc, 1.f, dq + (tok0 + query) * lddq + (int64_t)h * D, qvalid, lane);
-}
-
-// ------------------------------------------------------------------------------------------------ dK/dV pass (key-major)
-// A wave owns 32 keys of one kv head; all q heads of the group and the query tiles kb .. min(S - 1, k_last + W - 1) are walked.
-template <int D>
-__global__ __launch_bounds__(256) void swa_bwd_dkv_kernel(int S, int Hq, int Hkv, int W, const bf16_t* __restrict__ q, int64_t ldq,
-                                                          const bf16_t* __restrict__ k, int64_t ldk, const bf16_t* __restrict__ v, int64_t ldv,
-                                                          const bf16_t* __restrict__ d_o, int64_t lddo, const float* __restrict__ lse,
-                                                          const float* __restrict__ delta, bf16_t* __restrict__ dk, int64_t lddk,
-                                                          bf16_t* __restrict__ dv, int64_t lddv, float scale) {
-    using C = Tile32<D>;
-    constexpr int NDT = C::DT;
-    __shared__ __attribute__((aligned(16))) char smem[2 * C::IMG];
-    __shared__ float stat[2][32];
-    char* qimg = smem;
-    char* gimg = smem + C::IMG;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.z, hkv = blockIdx.y, rep = Hq / Hkv;
-    const int kb = blockIdx.x * 128;
-    const int k0 = kb + wave * 32;
-    const int key = k0 + (lane & 31);
-    const bool kvalid = key < S;
-    const int64_t tok0 = (int64_t)b * S;
-    bf16x8 kf[C::KS], vf[C::KS];
-    load_row_frags<D>(k + (tok0 + key) * ldk + (int64_t)hkv * D, kvalid, lane, kf);
-    load_row_frags<D>(v + (tok0 + key) * ldv + (int64_t)hkv * D, kvalid, lane, vf);
-    const float scale_log2 = scale * LOG2E;
-    f32x16 adk[NDT], adv[NDT];
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) adk[dt][i] = adv[dt][i] = 0.f;
-    const int klast = (kb + 127 < S ? kb + 127 : S - 1);
-    const int qend = (klast + W - 1 < S - 1 ? klast + W - 1 : S - 1);  // last query that sees a key of this workgroup
-    for (int hq = hkv * rep; hq < (hkv + 1) * rep; ++hq) {
-        for (int qt = kb / 32; qt <= qend / 32; ++qt) {
-            const int qs = qt * 32;
-            __syncthreads();
-            load_tile<D, 256>(qimg, q + (tok0 + qs) * ldq + (int64_t)hq * D, ldq, S - qs, threadIdx.x);
-            load_tile<D, 256>(gimg, d_o + (tok0 + qs) * lddo + (int64_t)hq * D, lddo, S - qs, threadIdx.x);
-            if (threadIdx.x < 32) {
-                const bool okq = qs + threadIdx.x < S;
-                stat[0][threadIdx.x] = okq ? lse[((int64_t)b * Hq + hq) * S + qs + threadIdx.x] * LOG2E : 0.f;
-                stat[1][threadIdx.x] = okq ? delta[((int64_t)b * Hq + hq) * S + qs + threadIdx.x] : 0.f;
-            }
-            __syncthreads();
-            // every query of the tile precedes this wave's keys, or the tile starts past the window of its last key
-            if (k0 >= S || qs + 31 < k0 || qs >= k0 + 31 + W) continue;
-            f32x16 s, dp;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < C::KS; ++ks) {
-                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(qimg, ks, lane), kf[ks], s, 0, 0, 0);
-                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(gimg, ks, lane), vf[ks], dp, 0, 0, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int r = 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3);
-                const int qi = qs + r;
-                const bool ok = kvalid && qi < S && key <= qi && key + W > qi;
-                const float p = ok ? exp2f(s[i] * scale_log2 - stat[0][r]) : 0.f;
-                s[i] = p;
-                dp[i] = p * (dp[i] - stat[1][r]) * scale;
-            }
-            const bf16x8 p0 = pack_frag(s, 0), p1 = pack_frag(s, 1), d0 = pack_frag(dp, 0), d1 = pack_frag(dp, 1);
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) {
-                adv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(gimg, 32 * dt, 0, lane), p0, adv[dt], 0, 0, 0);
-                adv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(gimg, 32 * dt, 16, lane), p1, adv[dt], 0, 0, 0);
-                adk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(qimg, 32 * dt, 0, lane), d0, adk[dt], 0, 0, 0);
-                adk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols<D>(qimg, 32 * dt, 16, lane), d1, adk[dt], 0, 0, 0);
-            }
-        }
-    }
-    store_t_tiles<NDT>(adk, 1.f, dk + (tok0 + key) * lddk + (int64_t)hkv * D, kvalid, lane);
-    store_t_tiles<NDT>(adv, 1.f, dv + (tok0 + key) * lddv + (int64_t)hkv * D, kvalid, lane);
-}
-
-// the kernels move 16 bytes at a time: every operand pointer must be 16-byte aligned (NULL passes here and is refused by the null check)
-bool aligned16(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if ((uintptr_t)p & 15) return false;
-    return true;
-}
-
-int check_swa(const char* who, int B, int S, int Hq, int Hkv, int D, int W, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo) {
-    MI355_REQUIRE(B >= 0 && S >= 0, "%s: negative batch or sequence length", who);
-    MI355_REQUIRE(W >= 1, "%s: window %d must be at least 1", who, W);
-    MI355_REQUIRE(Hq > 0 && Hkv > 0 && Hq % Hkv == 0, "%s: query heads (%d) must be a multiple of kv heads (%d)", who, Hq, Hkv);
-    MI355_REQUIRE(D == 32 || D == 64 || D == 128, "%s: head_dim %d not built (32, 64, 128)", who, D);
-    MI355_REQUIRE(ldq >= (int64_t)Hq * D && ldo >= (int64_t)Hq * D && ldk >= (int64_t)Hkv * D && ldv >= (int64_t)Hkv * D,
-                  "%s: leading dimension smaller than heads*head_dim", who);
-    MI355_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0, "%s: leading dimensions must be multiples of 8 elements", who);
-    // S <= 2^30 - 64: with W clamped to S the largest index sum in the kernels, k0 + 31 + W < 2 S + 32, stays inside int
-    MI355_REQUIRE(B <= 65535 && Hq <= 65535 && S <= (1 << 30) - 64, "%s: grid limits (B, Hq <= 65535, S <= 2^30 - 64)", who);
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------ row helpers
-inline int row_grid(int64_t rows) {
-    int64_t g = (rows + 3) / 4;
-    return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
 
 // ------------------------------------------------------------------------------------------------ Gemma RMSNorm
 __global__ __launch_bounds__(256) void g3_rmsnorm_fwd_kernel(int64_t rows, int width, const bf16_t* __restrict__ x, const bf16_t* __restrict__ res,
@@ -468,62 +216,9 @@ __global__ __launch_bounds__(256) void g3_geglu_bwd_kernel(int64_t tokens, int F
     }
 }
 
-inline int flat_grid(int64_t items) {
-    int64_t g = (items + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
-}
-
 }  // namespace
 
 #define ST(s) ((hipStream_t)(s))
-
-extern "C" int mi355_swa_attn_fwd(int B, int S, int Hq, int Hkv, int D, int W, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
-                                  int64_t ldv, void* o, int64_t ldo, float* lse, float scale, void* stream) {
-    if (check_swa("mi355_swa_attn_fwd", B, S, Hq, Hkv, D, W, ldq, ldk, ldv, ldo)) return 1;
-    if (B == 0 || S == 0) return 0;
-    MI355_REQUIRE(q && k && v && o && lse, "mi355_swa_attn_fwd: null pointer");
-    MI355_REQUIRE(aligned16({q, k, v, o}), "mi355_swa_attn_fwd: q, k, v, o must be 16-byte aligned");
-    const int w = W < S ? W : S;
-    dim3 grid((S + 127) / 128, Hq, B);
-#define LAUNCH(DD) swa_fwd_kernel<DD><<<grid, 256, 0, ST(stream)>>>(S, Hq, Hkv, w, (const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, lse, scale * LOG2E)
-    switch (D) {
-        case 32: LAUNCH(32); break;
-        case 64: LAUNCH(64); break;
-        default: LAUNCH(128); break;
-    }
-#undef LAUNCH
-    MI355_LAUNCH_CHECK("mi355_swa_attn_fwd");
-    return 0;
-}
-
-extern "C" int mi355_swa_attn_bwd(int B, int S, int Hq, int Hkv, int D, int W, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
-                                  int64_t ldv, const void* o, int64_t ldo, const void* d_o, int64_t lddo, const float* lse, float* delta, void* dq,
-                                  int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, float scale, void* stream) {
-    if (check_swa("mi355_swa_attn_bwd", B, S, Hq, Hkv, D, W, ldq, ldk, ldv, ldo)) return 1;
-    if (check_swa("mi355_swa_attn_bwd", B, S, Hq, Hkv, D, W, lddq, lddk, lddv, lddo)) return 1;
-    if (B == 0 || S == 0) return 0;
-    MI355_REQUIRE(q && k && v && o && d_o && lse && delta && dq && dk && dv, "mi355_swa_attn_bwd: null pointer");
-    MI355_REQUIRE(aligned16({q, k, v, d_o, dq, dk, dv}), "mi355_swa_attn_bwd: q, k, v, d_o, dq, dk, dv must be 16-byte aligned");
-    const int w = W < S ? W : S;
-    const int64_t tokens = (int64_t)B * S;
-    const int64_t dg = (tokens * Hq + 3) / 4;
-    attn_delta_kernel<<<(int)(dg > 8192 ? 8192 : dg), 256, 0, ST(stream)>>>(tokens, S, Hq, D, (const bf16_t*)o, ldo, (const bf16_t*)d_o, lddo, delta);
-    MI355_LAUNCH_CHECK("mi355_swa_attn_bwd(delta)");
-    dim3 gq((S + 127) / 128, Hq, B), gk((S + 127) / 128, Hkv, B);
-#define LAUNCH(DD)                                                                                                                                          \
-    swa_bwd_dq_kernel<DD><<<gq, 256, 0, ST(stream)>>>(S, Hq, Hkv, w, (const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (const bf16_t*)d_o, \
-                                                      lddo, lse, delta, (bf16_t*)dq, lddq, scale);                                                          \
-    swa_bwd_dkv_kernel<DD><<<gk, 256, 0, ST(stream)>>>(S, Hq, Hkv, w, (const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv,                   \
-                                                       (const bf16_t*)d_o, lddo, lse, delta, (bf16_t*)dk, lddk, (bf16_t*)dv, lddv, scale)
-    switch (D) {
-        case 32: LAUNCH(32); break;
-        case 64: LAUNCH(64); break;
-        default: LAUNCH(128); break;
-    }
-#undef LAUNCH
-    MI355_LAUNCH_CHECK("mi355_swa_attn_bwd");
-    return 0;
-}
 
 extern "C" int mi355_g3_rmsnorm_fwd(int64_t rows, int width, const void* x, const void* residual, const void* scale, void* y, float eps, void* stream) {
     MI355_REQUIRE(rows >= 0 && width > 0 && (width & 7) == 0, "mi355_g3_rmsnorm_fwd: width must be a positive multiple of 8 (got %d)", width);

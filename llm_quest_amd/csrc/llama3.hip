@@ -4,14 +4,14 @@
 //   rotation of dq, dk written into the q | k columns of d(qkv).  The arithmetic is that of rope_dropout.hip's bf16 path, rounding for rounding
 //   (cos / sin rounded to bf16, each product and the sum rounded to bf16): the two agree bit for bit.
 // Per-head maximum attention logit: out[h] = max over b and the visible (i, j) of scale * <q[b,i,h,:], k[b,j,h / (Hq / Hkv),:]>, visible = j <= i and
-//   key_mask[b,j] != 0 -- the pairs the softmax of mi355_attn_fwd sees.  The first half of gemma3.hip's forward and nothing else: S^T = K Q^T with the
+//   key_mask[b,j] != 0 -- the pairs the softmax of mi355_attn_fwd sees.  The first half of attention_band.hip's forward and nothing else: S^T = K Q^T with the
 //   query on the MFMA lane (mfma_f32_32x32x16_bf16, fp32 accumulation), one plain padded LDS image of 32 keys per barrier pair, only the key tiles up to
 //   the workgroup's diagonal.  No exp, no second product, no value tile; a workgroup of 128 queries leaves ONE float, and a second kernel folds the
 //   B * ceil(S / 128) partials of each head.  No atomics.  A NaN among the visible logits of a head makes its result NaN (torch.amax); a head without a
 //   visible pair yields -inf.
 // QK-Clip: w = bf16(float(w) * s) on the D x d_in row block of every head that clips; gamma is computed on the device from the [Hq] maxima, a workgroup
 //   whose head does not clip returns before it touches memory.
-#include <initializer_list>
+#include "host_checks.h"
 
 #include "attn_tile32.h"
 
@@ -118,13 +118,11 @@ __global__ __launch_bounds__(256) void max_logit_kernel(int S, int Hq, int Hkv, 
         const unsigned vis = (unsigned)__ballot(kvis);
         if (vis == 0u) continue;
         f32x16 s;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s[i] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < C::KS; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(kimg, ks, lane), qf[ks], s, 0, 0, 0);
+        zero_tile(s);
+        mma_rows<D>(s, kimg, qf, lane);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int kl = 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3);
+            const int kl = acc_row(i, lane);
             const bool ok = ((vis >> kl) & 1u) && key0 + kl <= query;
             const float v = s[i] * scale;
             nan_seen |= ok && v != v;
@@ -198,22 +196,11 @@ __global__ __launch_bounds__(256) void qk_clip_kernel(int Hq, int Hkv, int64_t p
     }
 }
 
-bool aligned16(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if ((uintptr_t)p & 15) return false;
-    return true;
-}
-
 int check_heads(const char* who, int Hq, int Hkv, int D) {
     MI355_REQUIRE(Hq > 0 && Hkv > 0 && Hq % Hkv == 0, "%s: query heads (%d) must be a multiple of kv heads (%d)", who, Hq, Hkv);
     MI355_REQUIRE(Hq <= 65535, "%s: at most 65535 query heads", who);
     MI355_REQUIRE(D == 64 || D == 128, "%s: head_dim %d not built (64, 128)", who, D);
     return 0;
-}
-
-inline int flat_grid(int64_t items) {
-    int64_t g = (items + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
 }
 
 }  // namespace

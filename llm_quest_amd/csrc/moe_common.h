@@ -4,6 +4,7 @@
 #pragma once
 #include <initializer_list>
 
+#include "host_checks.h"
 #include "rows_bf16.h"
 
 constexpr int MOE_MAX_E = 128;  // two experts per lane in the route kernels
@@ -127,12 +128,6 @@ __device__ __forceinline__ float route_select_biased(const float (&pf)[2], const
 inline bool bias_dtype_ok(int dt) { return dt == MI355_DT_BF16 || dt == MI355_DT_F32; }
 
 // ------------------------------------------------------------------------------------------------ host checks
-inline bool aligned16(std::initializer_list<const void*> ps) {
-    for (const void* p : ps)
-        if ((uintptr_t)p & 15) return false;
-    return true;
-}
-
 inline int capped_grid(int64_t blocks) { return (int)(blocks < 1 ? 1 : (blocks > 16384 ? 16384 : blocks)); }
 
 // 1 <= k <= 8, k <= E <= 128, T * k + 64 * E < 2^31

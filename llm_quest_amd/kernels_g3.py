@@ -1,4 +1,4 @@
-"""Tensor-level launchers of the Gemma3 kernels (csrc/gemma3.hip); no autograd here.
+"""Tensor-level launchers of the Gemma3 kernels (windowed attention: csrc/attention_band.hip; row kernels: csrc/gemma3.hip); no autograd here.
 
 Written like ``kernels.py`` / ``kernels_hc.py``: every launcher checks shapes / strides / dtypes on the host before a pointer reaches the
 GPU, allocates its outputs with torch and enqueues on torch's current stream.  There is no CPU fallback.
@@ -17,37 +17,62 @@ HEAD_DIMS = (32, 64, 128)
 RMS_EPS, LN_EPS = 1e-6, 1e-5
 
 
-def _attn_operand(t, name, tokens, width):
+# ---- host checks of the banded attention family (csrc/attention_band.hip): kernels_mimo.py's sink launchers use them too.  ``who`` is the family
+# label of the error texts ("swa attention" / "sink attention"); D is the q / k head dim, DV the v / o head dim.
+def _attn_operand(who, t, name, tokens, width):
     if t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != tokens or t.shape[1] != width:
-        raise ValueError(f"swa attention: {name} must be bf16 [tokens={tokens}, {width}] with unit inner stride, got {t.dtype} {tuple(t.shape)} {t.stride()}")
+        raise ValueError(f"{who}: {name} must be bf16 [tokens={tokens}, {width}] with unit inner stride, got {t.dtype} {tuple(t.shape)} {t.stride()}")
     if tokens > 1 and (t.stride(0) < width or t.stride(0) % 8):
-        raise ValueError(f"swa attention: {name} row stride {t.stride(0)} must be a multiple of 8 and at least {width}")
+        raise ValueError(f"{who}: {name} row stride {t.stride(0)} must be a multiple of 8 and at least {width}")
     if t.data_ptr() % 16:
-        raise ValueError(f"swa attention: {name} must be 16-byte aligned")
+        raise ValueError(f"{who}: {name} must be 16-byte aligned")
 
 
-def _check_attn(B, S, Hq, Hkv, D, W):
+def _check_attn(who, B, S, Hq, Hkv, W, dims_error):
+    """``dims_error``: None, or what to say of head dims that the family does not build (reported in its old place among the checks)."""
     if B < 0 or S < 0:
-        raise ValueError(f"swa attention: negative batch or sequence length ({B}, {S})")
+        raise ValueError(f"{who}: negative batch or sequence length ({B}, {S})")
     if W < 1:
-        raise ValueError(f"swa attention: window must be at least 1, got {W}")
-    if D not in HEAD_DIMS:
-        raise ValueError(f"swa attention: head_dim {D} not built {HEAD_DIMS}")
+        raise ValueError(f"{who}: window must be at least 1, got {W}")
+    if dims_error:
+        raise ValueError(f"{who}: {dims_error}")
     if Hq <= 0 or Hkv <= 0 or Hq % Hkv:
-        raise ValueError(f"swa attention: query heads ({Hq}) must be a multiple of kv heads ({Hkv})")
+        raise ValueError(f"{who}: query heads ({Hq}) must be a multiple of kv heads ({Hkv})")
+
+
+def _fwd_operands(who, q, k, v, B, S, Hq, Hkv, D, DV):
+    _attn_operand(who, q, "q", B * S, Hq * D)
+    _attn_operand(who, k, "k", B * S, Hkv * D)
+    _attn_operand(who, v, "v", B * S, Hkv * DV)
+
+
+def _bwd_operands(who, q, k, v, o, do, lse, dq, dk, dv, B, S, Hq, Hkv, D, DV):
+    """Checks the backward's operands; dq / dk / dv that are None are allocated.  Returns (dq, dk, dv)."""
+    dev = q.device
+    dq = torch.empty((B * S, Hq * D), dtype=BF16, device=dev) if dq is None else dq
+    dk = torch.empty((B * S, Hkv * D), dtype=BF16, device=dev) if dk is None else dk
+    dv = torch.empty((B * S, Hkv * DV), dtype=BF16, device=dev) if dv is None else dv
+    for t, n, w in ((q, "q", Hq * D), (k, "k", Hkv * D), (v, "v", Hkv * DV), (o, "o", Hq * DV), (do, "do", Hq * DV), (dq, "dq", Hq * D), (dk, "dk", Hkv * D),
+                    (dv, "dv", Hkv * DV)):
+        _attn_operand(who, t, n, B * S, w)
+    if not (lse.dtype == F32 and lse.is_contiguous() and tuple(lse.shape) == (B, Hq, S)):
+        raise ValueError(f"{who}: lse must be contiguous fp32 [B,Hq,S]")
+    return dq, dk, dv
 
 
 def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
+def _dims_error(D):
+    return None if D in HEAD_DIMS else f"head_dim {D} not built {HEAD_DIMS}"
+
+
 def swa_attn_fwd(q, k, v, B, S, Hq, Hkv, D, W, scale=None):
     """Sliding-window causal attention.  Returns (o [B*S, Hq*D] bf16, lse fp32 [B, Hq, S])."""
     L.require_gpu(q, k, v)
-    _check_attn(B, S, Hq, Hkv, D, W)
-    _attn_operand(q, "q", B * S, Hq * D)
-    _attn_operand(k, "k", B * S, Hkv * D)
-    _attn_operand(v, "v", B * S, Hkv * D)
+    _check_attn("swa attention", B, S, Hq, Hkv, W, _dims_error(D))
+    _fwd_operands("swa attention", q, k, v, B, S, Hq, Hkv, D, D)
     o = torch.empty((B * S, Hq * D), dtype=BF16, device=q.device)
     lse = torch.empty((B, Hq, S), dtype=F32, device=q.device)
     scale = D ** -0.5 if scale is None else scale
@@ -58,15 +83,8 @@ def swa_attn_fwd(q, k, v, B, S, Hq, Hkv, D, W, scale=None):
 def swa_attn_bwd(q, k, v, o, do, lse, B, S, Hq, Hkv, D, W, dq=None, dk=None, dv=None, scale=None):
     """dq / dk / dv: caller-provided (possibly row-strided) destinations, or new tensors.  Returns (dq, dk, dv)."""
     L.require_gpu(q, k, v, o, do, lse, dq, dk, dv)
-    _check_attn(B, S, Hq, Hkv, D, W)
-    dev = q.device
-    dq = torch.empty((B * S, Hq * D), dtype=BF16, device=dev) if dq is None else dq
-    dk = torch.empty((B * S, Hkv * D), dtype=BF16, device=dev) if dk is None else dk
-    dv = torch.empty((B * S, Hkv * D), dtype=BF16, device=dev) if dv is None else dv
-    for t, n, w in ((q, "q", Hq), (k, "k", Hkv), (v, "v", Hkv), (o, "o", Hq), (do, "do", Hq), (dq, "dq", Hq), (dk, "dk", Hkv), (dv, "dv", Hkv)):
-        _attn_operand(t, n, B * S, w * D)
-    if not (lse.dtype == F32 and lse.is_contiguous() and tuple(lse.shape) == (B, Hq, S)):
-        raise ValueError("swa attention: lse must be contiguous fp32 [B,Hq,S]")
+    _check_attn("swa attention", B, S, Hq, Hkv, W, _dims_error(D))
+    dq, dk, dv = _bwd_operands("swa attention", q, k, v, o, do, lse, dq, dk, dv, B, S, Hq, Hkv, D, D)
     delta = torch.empty_like(lse)
     scale = D ** -0.5 if scale is None else scale
     L.call("mi355_swa_attn_bwd", B, S, Hq, Hkv, D, min(int(W), 2**31 - 1), L.ptr(q), _ld(q), L.ptr(k), _ld(k), L.ptr(v), _ld(v), L.ptr(o), _ld(o), L.ptr(do), _ld(do),

@@ -1,4 +1,4 @@
-"""Tensor-level launchers of the MiMo-V2-Flash kernels (csrc/mimo.hip); no autograd here.
+"""Tensor-level launchers of the MiMo-V2-Flash kernels (sink attention: csrc/attention_band.hip; norm + RoPE: csrc/mimo.hip); no autograd here.
 
 Written like ``kernels_g3.py``: every launcher checks shapes / strides / dtypes on the host before a pointer reaches the GPU, allocates its
 outputs with torch and enqueues on torch's current stream.  There is no CPU fallback.
@@ -12,36 +12,24 @@ import torch
 
 from . import _lib as L
 from . import kernels as K
+from . import kernels_g3 as KG
+from .kernels_g3 import _ld
 
 BF16, F32 = torch.bfloat16, torch.float32
 MIMO_PARTS = 512  # max workgroups (= rows of partials) of the backwards that reduce parameter gradients
 HEAD_DIM_PAIRS = ((64, 32), (64, 64), (128, 64), (128, 128), (192, 128))  # (head_dim, value_head_dim)
 NORM_HEAD_DIMS = (64, 128, 192)
 RMS_EPS = 1e-6
+WHO = "sink attention"  # the family label in the error texts of the attention host checks, which are kernels_g3's
+
+
+def _pair_error(D, DV):
+    return None if (D, DV) in HEAD_DIM_PAIRS else f"(head_dim, value_head_dim) = ({D}, {DV}) not built {HEAD_DIM_PAIRS}"
 
 
 def check_pair(D, DV, what="sink attention"):
-    if (D, DV) not in HEAD_DIM_PAIRS:
-        raise ValueError(f"{what}: (head_dim, value_head_dim) = ({D}, {DV}) not built {HEAD_DIM_PAIRS}")
-
-
-def _attn_operand(t, name, tokens, width):
-    if t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != tokens or t.shape[1] != width:
-        raise ValueError(f"sink attention: {name} must be bf16 [tokens={tokens}, {width}] with unit inner stride, got {t.dtype} {tuple(t.shape)} {t.stride()}")
-    if tokens > 1 and (t.stride(0) < width or t.stride(0) % 8):
-        raise ValueError(f"sink attention: {name} row stride {t.stride(0)} must be a multiple of 8 and at least {width}")
-    if t.data_ptr() % 16:
-        raise ValueError(f"sink attention: {name} must be 16-byte aligned")
-
-
-def _check_attn(B, S, Hq, Hkv, D, DV, W):
-    if B < 0 or S < 0:
-        raise ValueError(f"sink attention: negative batch or sequence length ({B}, {S})")
-    if W < 1:
-        raise ValueError(f"sink attention: window must be at least 1, got {W}")
-    check_pair(D, DV)
-    if Hq <= 0 or Hkv <= 0 or Hq % Hkv:
-        raise ValueError(f"sink attention: query heads ({Hq}) must be a multiple of kv heads ({Hkv})")
+    if _pair_error(D, DV):
+        raise ValueError(f"{what}: {_pair_error(D, DV)}")
 
 
 def _sink_f32(sink, Hq):
@@ -54,17 +42,11 @@ def _sink_f32(sink, Hq):
     return sink.contiguous() if sink.dtype == F32 else K.cast(sink.contiguous(), F32)
 
 
-def _ld(t):
-    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-
-
 def sink_attn_fwd(q, k, v, B, S, Hq, Hkv, D, DV, W, sink=None, scale=None):
     """Causal / sliding-window attention with an optional sink.  Returns (o [B*S, Hq*DV] bf16, lse fp32 [B, Hq, S], the sink included)."""
     L.require_gpu(q, k, v, sink)
-    _check_attn(B, S, Hq, Hkv, D, DV, W)
-    _attn_operand(q, "q", B * S, Hq * D)
-    _attn_operand(k, "k", B * S, Hkv * D)
-    _attn_operand(v, "v", B * S, Hkv * DV)
+    KG._check_attn(WHO, B, S, Hq, Hkv, W, _pair_error(D, DV))
+    KG._fwd_operands(WHO, q, k, v, B, S, Hq, Hkv, D, DV)
     z = _sink_f32(sink, Hq)
     o = torch.empty((B * S, Hq * DV), dtype=BF16, device=q.device)
     lse = torch.empty((B, Hq, S), dtype=F32, device=q.device)
@@ -79,16 +61,8 @@ def sink_attn_bwd(q, k, v, o, do, lse, B, S, Hq, Hkv, D, DV, W, sink=None, dq=No
     """dq / dk / dv: caller-provided (possibly row-strided) destinations, or new tensors.  Returns (dq, dk, dv, dsink): dsink fp32 [Hq]
     (per-workgroup partial rows folded in a fixed order), None without a sink."""
     L.require_gpu(q, k, v, o, do, lse, dq, dk, dv, sink)
-    _check_attn(B, S, Hq, Hkv, D, DV, W)
-    dev = q.device
-    dq = torch.empty((B * S, Hq * D), dtype=BF16, device=dev) if dq is None else dq
-    dk = torch.empty((B * S, Hkv * D), dtype=BF16, device=dev) if dk is None else dk
-    dv = torch.empty((B * S, Hkv * DV), dtype=BF16, device=dev) if dv is None else dv
-    for t, n, w in ((q, "q", Hq * D), (k, "k", Hkv * D), (v, "v", Hkv * DV), (o, "o", Hq * DV), (do, "do", Hq * DV), (dq, "dq", Hq * D), (dk, "dk", Hkv * D),
-                    (dv, "dv", Hkv * DV)):
-        _attn_operand(t, n, B * S, w)
-    if not (lse.dtype == F32 and lse.is_contiguous() and tuple(lse.shape) == (B, Hq, S)):
-        raise ValueError("sink attention: lse must be contiguous fp32 [B,Hq,S]")
+    KG._check_attn(WHO, B, S, Hq, Hkv, W, _pair_error(D, DV))
+    dq, dk, dv = KG._bwd_operands(WHO, q, k, v, o, do, lse, dq, dk, dv, B, S, Hq, Hkv, D, DV)
     z = _sink_f32(sink, Hq)
     delta = torch.empty_like(lse)
     scale = D ** -0.5 if scale is None else scale
@@ -97,7 +71,7 @@ def sink_attn_bwd(q, k, v, o, do, lse, B, S, Hq, Hkv, D, DV, W, sink=None, dq=No
         parts = min(MIMO_PARTS, max(1, (B * S + 255) // 256)) if parts is None else parts
         if parts < 1:
             raise ValueError(f"sink attention: parts must be positive, got {parts}")
-        part = (torch.zeros if B * S == 0 else torch.empty)((parts, Hq), dtype=F32, device=dev)
+        part = (torch.zeros if B * S == 0 else torch.empty)((parts, Hq), dtype=F32, device=q.device)
     L.require_gpu(q, k, v, o, do, lse, dq, dk, dv, z)
     L.call("mi355_sink_attn_bwd", B, S, Hq, Hkv, D, DV, min(int(W), 2**31 - 1), L.ptr(q), _ld(q), L.ptr(k), _ld(k), L.ptr(v), _ld(v), L.ptr(o), _ld(o), L.ptr(do),
            _ld(do), L.ptr(z), L.ptr(lse), L.ptr(delta), L.ptr(dq), _ld(dq), L.ptr(dk), _ld(dk), L.ptr(dv), _ld(dv), L.ptr(part), 0 if part is None else parts, scale)

@@ -2,7 +2,7 @@
 GroupedQueryAttention with the local / global layer schedule.
 
 The reference materialises a [b, h, s, w, d] gather of key / value windows; here a windowed layer runs ``mi355_swa_attn_fwd/_bwd``
-(csrc/gemma3.hip), which walks only the key tiles inside the band and never reads ``swa_mask`` or ``mask``.
+(csrc/attention_band.hip), which walks only the key tiles inside the band and never reads ``swa_mask`` or ``mask``.
 """
 
 import torch

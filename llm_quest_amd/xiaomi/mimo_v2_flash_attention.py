@@ -1,7 +1,7 @@
 """Grouped-query attention with an attention sink -- API of ``llm_quest/xiaomi/mimo_v2_flash_attention.py`` (bf16 training path, no-grad forward).
 
 The reference builds the dense score matrix, masks it, appends one sink column per head for the softmax and slices it off again; here the core is
-``mi355_sink_attn_fwd/_bwd`` (csrc/mimo.hip): the band is computed from indices, the sink is the initial state of the online softmax, the v / o
+``mi355_sink_attn_fwd/_bwd`` (csrc/attention_band.hip): the band is computed from indices, the sink is merged into the online softmax's state once behind the key loop (one more key without a value), the v / o
 heads have their own width, and ``mask`` is never read inside the model (``TransformerBlock`` hands the window over as a number).  Called on its
 own, the module has only the mask to learn the window from: it is read once per mask on the host (``ops_mimo.window_of``) and must be the causal mask
 or a sliding-window band.

@@ -1,5 +1,5 @@
 """Plain-torch restatement of the Gemma3 arithmetic, written from the formulas of the kernels' contract (include/mi355_vlm.h,
-csrc/gemma3.hip).  TEST INFRASTRUCTURE ONLY: one function per kernel, plus a block and a model.
+csrc/attention_band.hip, csrc/gemma3.hip).  TEST INFRASTRUCTURE ONLY: one function per kernel, plus a block and a model.
 
 Every function runs in one of two flows:
   * ``exact=False``: the reference's dtype flow -- bf16 tensors, every torch op rounding its result to bf16 where the reference's

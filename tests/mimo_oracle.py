@@ -1,5 +1,5 @@
 """Plain-torch restatement of the MiMo-V2-Flash arithmetic, written from the formulas of the kernels' contract (include/mi355_vlm.h,
-csrc/mimo.hip): attention with a sink and its own value head dim, the per-head RMSNorm + partial RoPE, the block and the model with its MTP
+csrc/attention_band.hip, csrc/mimo.hip): attention with a sink and its own value head dim, the per-head RMSNorm + partial RoPE, the block and the model with its MTP
 modules.  TEST INFRASTRUCTURE ONLY.  The mixture-of-experts layer is tests/deepseek_moe_oracle.py's (0 shared experts).
 
 Every function runs in one of two flows:

@@ -1,4 +1,4 @@
-"""Gemma3 kernels (csrc/gemma3.hip) and Gemma3Model on the GPU, against the plain-torch restatement (tests/gemma3_oracle.py) and the
+"""Gemma3 kernels (csrc/attention_band.hip, csrc/gemma3.hip) and Gemma3Model on the GPU, against the plain-torch restatement (tests/gemma3_oracle.py) and the
 reference fixture (tests/golden/gemma3_tiny*.safetensors).
 
 Tolerance: the project's 1.5x rule and nothing else -- the relative L2 distance of a kernel output to the fp64

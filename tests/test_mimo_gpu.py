@@ -1,4 +1,4 @@
-"""MiMo-V2-Flash kernels (csrc/mimo.hip) and MiMoModel on the GPU, against the plain-torch restatement (tests/mimo_oracle.py) and the reference
+"""MiMo-V2-Flash kernels (csrc/attention_band.hip, csrc/mimo.hip) and MiMoModel on the GPU, against the plain-torch restatement (tests/mimo_oracle.py) and the reference
 fixture (tests/golden/mimo_tiny*.safetensors).
 
 Tolerance: the project's 1.5x rule exactly as tests/test_gemma3_gpu.py's ``judge`` implements it, and nothing else -- the
@@ -171,6 +171,26 @@ def test_attention_backward_is_bit_reproducible():
     judge("dsink (2 workgroups)", small["dsink"], c[False]["dsink"], c[True]["dsink"], bad)
     _same_bits(small, _run_attn(*c["ops"], 100, parts=2))
     assert not bad, "\n".join(bad)
+
+
+@pytest.mark.parametrize("W", [1, 33, 130])
+@pytest.mark.parametrize("D", [64, 128])
+def test_the_windowed_entry_points_are_the_sink_kernels_at_equal_head_dims_without_a_sink(D, W):
+    """mi355_swa_attn_* and mi355_sink_attn_* at DV = D without a sink are two ABI names of one kernel (csrc/attention_band.hip): same bits.
+    S = 130 is two query blocks, the second of two rows, and five key tiles, the last ragged; W crosses one key, a tile edge and W = S."""
+    from llm_quest_amd import kernels_g3 as KG
+
+    KM = _km()
+    B, S, Hq, Hkv = 2, 130, 4, 2
+    q, k, v, do = [O.to_tokens(t).cuda() for t in O.attn_operands(B, S, Hq, Hkv, D, D, seed=9100 + D, sink=False)[:4]]
+    o_s, lse_s = KM.sink_attn_fwd(q, k, v, B, S, Hq, Hkv, D, D, W)
+    o_w, lse_w = KG.swa_attn_fwd(q, k, v, B, S, Hq, Hkv, D, W)
+    assert torch.equal(o_s, o_w) and torch.equal(lse_s, lse_w)
+    dq_s, dk_s, dv_s, dz = KM.sink_attn_bwd(q, k, v, o_s, do, lse_s, B, S, Hq, Hkv, D, D, W)
+    dq_w, dk_w, dv_w = KG.swa_attn_bwd(q, k, v, o_w, do, lse_w, B, S, Hq, Hkv, D, W)
+    assert dz is None
+    assert torch.equal(dq_s, dq_w) and torch.equal(dk_s, dk_w) and torch.equal(dv_s, dv_w)
+    assert float(o_s.float().abs().sum()) > 0 and float(dk_s.float().abs().sum()) > 0  # the launches wrote something
 
 
 @pytest.mark.parametrize("B,S,Hq,Hkv,D,DV,W", [(1, 1, 2, 1, 64, 32, 1), (2, 70, 6, 2, 64, 32, 5), (1, 129, 4, 2, 128, 64, 33), (1, 40, 2, 1, 192, 128, 16)])

@@ -3,9 +3,8 @@
     python tools/bench_mimo.py [--batch 8] [--steps 8] [--warmup 3] [--out profiles/mimo_bench.json]
 
 (a) Sink attention forward and forward + backward (bf16) at MIMO_V2_SMALL_CONFIG's sliding-window shape (S = 512, 12 query heads over 4 kv heads,
-    head dims 64 / 32, W = 128, a sink) and at a long shape (S = 4096), each beside the same kernels at W = S; and at head dims 64 / 64 without a
-    sink beside ``kernels_g3.swa_attn_*`` on the same operands: the sink is only the initial state of the online softmax, so that pair shows what
-    the <D, DV> form and the sink cost.
+    head dims 64 / 32, W = 128, a sink) and at a long shape (S = 4096), each beside the same kernels at W = S.  (``kernels_g3.swa_attn_*`` are
+    the same kernels at DV = D without a sink -- csrc/attention_band.hip -- so there is no windowed counterpart to time them against.)
 (b) The training step (forward + loss + backward, MTP on) of ``MiMoModel(MIMO_V2_SMALL_CONFIG).to(bfloat16)`` as written, against the same
     model with window_size = context_length (every layer walks the whole causal triangle).
 
@@ -59,8 +58,7 @@ def attention_flops(B, S, Hq, D, DV, W, backward):
     return fwd + (bwd if backward else 0)
 
 
-def measure_attention(B, S, Hq, Hkv, D, DV, W, sink, rounds, inner, with_g3):
-    from llm_quest_amd import kernels_g3 as KG
+def measure_attention(B, S, Hq, Hkv, D, DV, W, sink, rounds, inner):
     from llm_quest_amd import kernels_mimo as KM
 
     g = torch.Generator().manual_seed(3)
@@ -77,16 +75,12 @@ def measure_attention(B, S, Hq, Hkv, D, DV, W, sink, rounds, inner, with_g3):
         return r[0], do, r[1]
 
     variants = {f"sink attention W={W}": mimo(W), f"sink attention W=S={S}": mimo(S)}
-    if with_g3:
-        for w in (W, S):
-            fwd = lambda w=w: KG.swa_attn_fwd(q, k, v, B, S, Hq, Hkv, D, w)
-            variants[f"gemma3 swa_attn W={w}"] = (fwd, lambda w=w, fwd=fwd: KG.swa_attn_bwd(q, k, v, *_ol(fwd()), B, S, Hq, Hkv, D, w, dq, dk, dv))
     f = time_alternating({n: fb[0] for n, fb in variants.items()}, rounds, 3, inner)
     fb = time_alternating({n: fb[1] for n, fb in variants.items()}, rounds, 3, inner)
     out = []
     for n in variants:
         w = S if "W=S" in n or n.endswith(f"W={S}") else W
-        r = dict(kind="attention", name=n, B=B, S=S, Hq=Hq, Hkv=Hkv, D=D, DV=DV, sink=bool(sink) and n.startswith("sink"), fwd_ms=f[n]["ms_median"], fwd_ms_min=f[n]["ms_min"],
+        r = dict(kind="attention", name=n, B=B, S=S, Hq=Hq, Hkv=Hkv, D=D, DV=DV, sink=bool(sink), fwd_ms=f[n]["ms_median"], fwd_ms_min=f[n]["ms_min"],
                  fwd_bwd_ms=fb[n]["ms_median"], fwd_bwd_ms_min=fb[n]["ms_min"], rounds=rounds, calls_per_round=inner)
         r["fwd_tflops"] = attention_flops(B, S, Hq, D, DV, w, False) / (r["fwd_ms"] * 1e-3) / 1e12
         r["fwd_bwd_tflops"] = attention_flops(B, S, Hq, D, DV, w, True) / (r["fwd_bwd_ms"] * 1e-3) / 1e12
@@ -161,9 +155,7 @@ def main():
     Hq, Hkv, D, DV, W = C["n_heads"], C["num_swa_kv_groups"], C["head_dim"], C["value_head_dim"], C["window_size"]
     shapes = [(args.batch, C["context_length"], 40), (2, 4096, 8)]  # (B, S, calls per timed window)
     for B, S, inner in shapes:
-        for r in measure_attention(B, S, Hq, Hkv, D, DV, W, True, args.kernel_rounds, inner, False):
-            emit(r)
-        for r in measure_attention(B, S, Hq, Hkv, D, D, W, False, args.kernel_rounds, inner, True):
+        for r in measure_attention(B, S, Hq, Hkv, D, DV, W, True, args.kernel_rounds, inner):
             emit(r)
     if not args.skip_model:
         for r in measure_steps(args.batch, args.steps, args.warmup):
