@@ -10,10 +10,11 @@ Judgement (``judge``): o, dq, dk, dv are cut into blocks of 32 consecutive token
 tail shorter than 32 joins the block before it.  A block passes when rel_l2(kernel, exact) <= max(1.5 * floor of that block, cap), and the whole
 tensor must satisfy the same formula.  The caps are the numbers the suite applies to whole tensors (test_kernels_gpu.py): 4e-3 for o, 8e-3 for the
 gradients.  (The plain 1.5 x floor + 2e-3 rule of the side kernels is not usable at tiny S, where the floor is near zero.)  Token rows whose exact
-value is identically zero have no relative distance: dk / dv of padded keys and dq of fully-masked rows must be exactly 0; dq of a row that sees
-one key, and dk at S = 1 (a one-key softmax: dS = P (dP - delta) with dP = dO . v and delta = dO . o), are bounded by one rounding of o entering
-delta, |dq_d| <= 2^-7 * scale * sum_e |dO_e v_e| * |k_d| and the mirror image for dk (``one_key_bounds``).  No block is left out: ``judge`` counts
-the blocks it judged and the blocks there are, and a zero block whose rows have no rule of their own is a failure.
+value is identically zero have no relative distance: dk / dv of padded keys and dq of fully-masked rows must be exactly 0.  A one-key softmax has
+dS = P (dP - delta) with dP = dO . v and delta = dO . o, so dq of a row that sees one key is bounded by one rounding of o entering delta,
+|dq_d| <= 2^-7 * scale * sum_e |dO_e v_e| * |k_d|.  dk of a key that only such rows see has the mirror image as its bound: at S = 1, and for
+every key of a window of one in tests/side_attention_sweep.py (``one_key_bounds``).  No block is left out: ``judge`` counts the blocks it judged
+and the blocks there are, and a zero block whose rows have no rule of their own is a failure.
 """
 
 import math
@@ -180,7 +181,9 @@ def judge_tensor(name, got, exact, floor, structural=None, one_key=None, cap=Non
     """One of o / dq / dk / dv, all [B, H, S, D]: ``got`` the implementation, ``exact`` fp64, ``floor`` the reference's bf16 result.
     ``structural``: bool [B, H, S], the token rows that are zero by the mask alone (padded keys for dk / dv, fully-masked queries for dq): where the
     exact row is zero too, the implementation's must be exactly 0.  ``one_key``: (rows bool [B, H, S], limit fp64 [B, H, S, D]) -- the rows of a
-    one-key softmax and the bound on their elements.  -> (worst block ratio, blocks judged, list of failure strings)."""
+    one-key softmax and the bound on their elements.  ``cap``: a number, or fp64 [B, H, number of blocks] where a class of blocks has a bound of its
+    own (the whole tensor is then held to the blocks' caps combined with the weights of their norms).
+    -> (worst block ratio, blocks judged, list of failure strings)."""
     cap = CAP[name] if cap is None else cap
     B, H, S, D = exact.shape
     got, exact, floor = got.double(), exact.double(), floor.double()
@@ -210,14 +213,17 @@ def judge_tensor(name, got, exact, floor, structural=None, one_key=None, cap=Non
         t0, t1 = block_edges(S)[i]
         if not bool(covered[b, h, t0:t1].all()):
             fails.append(f"{name}: sample {b}, head {h}, block {i}: the exact block is zero and no rule covers it")
-    bound = torch.maximum(1.5 * flo / ref.clamp_min(1e-300), torch.full_like(ref, cap))
+    caps = cap.to(ref.dtype).expand_as(ref) if torch.is_tensor(cap) else torch.full_like(ref, cap)
+    bound = torch.maximum(1.5 * flo / ref.clamp_min(1e-300), caps)
     ratio = torch.where(live, err / ref.clamp_min(1e-300) / bound, torch.zeros_like(ref))
     for b, h, i in (ratio > 1).nonzero().tolist():
         fails.append(f"{name}: sample {b}, head {h}, block {i} (tokens {block_edges(S)[i]}): rel l2 {float(err[b, h, i] / ref[b, h, i]):.3e} > "
-                     f"max(1.5 * {float(flo[b, h, i] / ref[b, h, i]):.3e}, {cap:.0e})")
+                     f"max(1.5 * {float(flo[b, h, i] / ref[b, h, i]):.3e}, {float(caps[b, h, i]):.0e})")
     worst = float(ratio.max())
     if bool(live.any()):  # the whole tensor under the same formula
         e, f, n = float((got - exact).norm()), float((floor - exact).norm()), float(exact.norm())
+        if torch.is_tensor(cap):
+            cap = float((caps * ref).norm()) / n
         whole = e / n / max(1.5 * f / n, cap)
         if whole > 1:
             fails.append(f"{name}: whole tensor rel l2 {e / n:.3e} > max(1.5 * {f / n:.3e}, {cap:.0e})")
@@ -225,37 +231,47 @@ def judge_tensor(name, got, exact, floor, structural=None, one_key=None, cap=Non
     return worst, int(ratio.numel()), fails
 
 
-def one_key_bounds(q, k, v, do, km, causal):
-    """The rows whose softmax runs over ONE key j (S = 1; the first query under the causal mask; the first query behind a padded head): P = 1,
-    dS = dO . v_j - delta, delta = dO . o with o = v_j up to one bf16 rounding, so |dS| <= 2^-7 sum_e |dO_e v_je| (the bound
-    test_attention_fullsize_invariants allows for that row) and |dq_d| <= scale |dS| |k_jd|.  At S = 1 the key's dk is the mirror image, summed over
-    its group's heads.  -> {"dq": (rows [B, Hq, S], limit [B, Hq, S, D]), "dk": the same for [B, Hkv, 1, D] at S = 1}"""
+def one_key_bounds(q, k, v, do, km, causal, allowed=None):
+    """The rows whose softmax runs over ONE key j (S = 1; the first query under the causal mask; the first query behind a padded head; every query
+    of a window of one): P = 1, dS = dO . v_j - delta, delta = dO . o with o = v_j up to one bf16 rounding, so |dS| <= 2^-7 sum_e |dO_e v_je| (the
+    bound test_attention_fullsize_invariants allows for that row) and |dq_d| <= scale |dS| |k_jd|.  A key j whose every query is such a row (S = 1;
+    every key of a window of one) has the mirror image as its dk: the sum of scale |dS_i| |q_id| over those queries and its group's heads.
+    ``allowed``: bool [B, S, S], True where query i sees key j, for masks that (km, causal) cannot state (it replaces them); v and do may be
+    narrower or wider than q and k.
+    -> {"dq": (rows [B, Hq, S], limit [B, Hq, S, D]), "dk": the same for [B, Hkv, S, D], present at S = 1 and wherever such a key exists}"""
     B, Hq, S, D = q.shape
     Hkv = k.shape[1]
     src = torch.arange(Hq) // (Hq // Hkv)
-    seen = ~blocked_pairs(B, S, km, causal)[:, 0]  # [B, S, S]
+    seen = ~blocked_pairs(B, S, km, causal)[:, 0] if allowed is None else allowed  # [B, S, S]
     rows = seen.sum(dim=-1) == 1
-    j = seen.int().argmax(dim=-1)[:, None, :, None].expand(B, Hq, S, D)
-    kj, vj = k.double()[:, src].gather(2, j), v.double()[:, src].gather(2, j)
+    j = seen.int().argmax(dim=-1)[:, None, :, None]
+    kj, vj = k.double()[:, src].gather(2, j.expand(B, Hq, S, D)), v.double()[:, src].gather(2, j.expand(B, Hq, S, v.shape[-1]))
     ds = 2.0 ** -7 * D ** -0.5 * (do.double() * vj).abs().sum(dim=-1, keepdim=True)
     out = {"dq": (rows[:, None, :].expand(B, Hq, S), ds * kj.abs())}
-    if S == 1:
-        out["dk"] = (rows[:, None, :].expand(B, Hkv, S), (ds * q.double().abs()).view(B, Hkv, Hq // Hkv, S, D).sum(dim=2))
+    lone = seen & rows[:, :, None]  # [B, query, key]: the query sees this key and no other
+    keys = lone.any(dim=1) & ~(seen & ~rows[:, :, None]).any(dim=1)  # [B, S]: seen, and by one-key rows only
+    if S == 1 or bool(keys.any()):
+        lim = torch.einsum("bij,bhid->bhjd", lone.double(), ds * q.double().abs())
+        out["dk"] = (keys[:, None, :].expand(B, Hkv, S), lim.view(B, Hkv, Hq // Hkv, S, D).sum(dim=2))
     return out
 
 
-def judge(got, exact, floor, km, causal, ops):
+def judge(got, exact, floor, km, causal, ops, allowed=None):
     """``got`` / ``exact`` / ``floor``: dicts with o, dq, dk, dv [B, H, S, D] (a missing key of ``got`` is not judged); ``km`` / ``causal``: the mask
-    of the case (the rows that must be exactly zero); ``ops`` = (q, k, v, do), for the bound of the one-key rows.
+    of the case (the rows that must be exactly zero); ``ops`` = (q, k, v, do), for the bound of the one-key rows.  ``allowed``: bool [B, S, S], the
+    pairs (query, key) that see each other, in place of (km, causal): a query that sees no key and a key that no query sees must be exactly zero.
     -> (worst ratio per tensor, blocks judged, blocks there are, failures)."""
     worst, judged, total, fails = {}, 0, 0, []
-    one_key = one_key_bounds(*ops, km, causal)
+    one_key = one_key_bounds(*ops, km, causal, allowed)
     for name in ("o", "dq", "dk", "dv"):
         if name not in got:
             continue
         structural = None
         B, H, S, _ = exact[name].shape
-        if name == "dq":
+        if allowed is not None:
+            if name != "o":
+                structural = (~allowed.any(dim=-1 if name == "dq" else 1))[:, None, :].expand(B, H, S)
+        elif name == "dq":
             structural = fully_masked_rows(B, S, km, causal)[:, None, :].expand(B, H, S)
         elif name in ("dk", "dv") and km is not None:
             structural = (~km.bool())[:, None, :].expand(B, H, S)

@@ -87,13 +87,14 @@ def silu(x):
 
 def mla_attention(q_nope, q_rope, k_nope, k_rope, v, dtype=None, scale=None):
     """q_nope / k_nope / v [B, H, S, Dn], q_rope [B, H, S, Dr], k_rope [B, S, Dr] (shared by the heads) -> (o [B, H, S, Dn], lse [B, H, S]).
-    s = scale * (q_nope . k_nope + q_rope . k_rope) over keys j <= i."""
+    s = scale * (q_nope . k_nope + q_rope . k_rope) over keys j <= i.  k_rope may also come as [B, H, S, Dr], the shared row already repeated per
+    head: a leaf of that shape receives every head's own share of the shared key's gradient (tests/side_attention_sweep.py)."""
     B, H, S, Dn = q_nope.shape
     Dr = q_rope.shape[-1]
     scale = (Dn + Dr) ** -0.5 if scale is None else scale
     q_nope, q_rope, k_nope, k_rope, v = [_c(t, dtype) for t in (q_nope, q_rope, k_nope, k_rope, v)]
     q = torch.cat((q_nope, q_rope), dim=-1)
-    k = torch.cat((k_nope, k_rope.unsqueeze(1).expand(-1, H, -1, -1)), dim=-1)
+    k = torch.cat((k_nope, k_rope if k_rope.dim() == 4 else k_rope.unsqueeze(1).expand(-1, H, -1, -1)), dim=-1)
     s = (q @ k.mT) * scale
     s = s.masked_fill(torch.ones(S, S, dtype=torch.bool).triu_(1), -torch.inf)
     p = F.softmax(s, dim=-1)
