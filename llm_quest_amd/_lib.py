@@ -184,6 +184,16 @@ SIGNATURES = {
     "mi355_llama_rope_bwd": [_L, _I, _I, _I, _P, _L, _P, _L, _P, _P, _L, _P, _P, _L, _P],
     "mi355_attn_max_logit": [_I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _F, _P, _L, _P, _P],
     "mi355_qk_clip": [_I, _I, _I, _L, _P, _P, _P, _F, _F, _I, _P],
+    # Reinforced Attention Learning: the head-mean attention distribution from q, k or from weights, its backward, the JSD rows, the reduction (csrc/ral.hip)
+    "mi355_ral_qk_prepare_fwd": [_I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _F, _P, _P, _P, _P],
+    "mi355_ral_qk_prepare_bwd": [_I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _F, _P, _P, _P, _P, _L, _P, _L, _P],
+    "mi355_ral_prepare_fwd": [_I, _I, _I, _P, _I, _P, _P, _P],
+    "mi355_ral_prepare_bwd": [_I, _I, _I, _P, _P, _I, _P],
+    "mi355_ral_renorm_bwd": [_I, _I, _P, _P, _P, _I, _P, _P],
+    "mi355_ral_jsd_fwd": [_I, _I, _P, _P, _P, _P],
+    "mi355_ral_jsd_bwd": [_I, _I, _P, _P, _P, _P, _P],
+    "mi355_ral_reduce": [_I, _I, _P, _P, _P, _F, _P, _P, _P, _P],
+    "mi355_ral_add_bf16": [_L, _P, _P, _P, _P],
 }
 # size / constant queries: no stream argument, the return value is the answer (name -> (argtypes, restype))
 QUERIES = {

@@ -7,7 +7,6 @@ from indices).  There is no QK-norm in this family, so its attention logits are 
 per-head maximum in ``max_attn_logit`` for ``common/qk_clip.py``.
 """
 
-import torch
 import torch.nn as nn
 
 from llm_quest_amd import ops_g3, ops_llama
@@ -19,7 +18,12 @@ class GroupedQueryAttention(nn.Module):
 
     ``track_max_attn_logit`` (a plain attribute, default False): when True every forward, in grad mode or not, also launches
     ``mi355_attn_max_logit`` on the post-RoPE q and k and stores the result in ``max_attn_logit`` (fp32 [num_heads] on the device, overwritten per
-    forward).  When False the forward launches nothing more than it would without the feature."""
+    forward).  When False the forward launches nothing more than it would without the feature.
+
+    ``expose_qk`` (a plain attribute, default False; ours): when True and grad mode is on, the autograd node of the forward (the block's, or this
+    module's when called on its own) returns the post-RoPE q [b * s, num_heads * head_dim] and k [b * s, num_kv_groups * head_dim] as two more
+    differentiable outputs and leaves them in ``exposed_qk`` (``common/reinforced_attention_learning.py`` reads them); gradients that arrive on them
+    join dq, dk ahead of the RoPE backward.  When False the node has one output and the forward launches what it launches without the feature."""
 
     def __init__(
         self,
@@ -49,10 +53,12 @@ class GroupedQueryAttention(nn.Module):
         self.out_proj = nn.Linear(d_out, d_out, dtype=dtype)
         self.track_max_attn_logit = False
         self.max_attn_logit = None
+        self.expose_qk = False
+        self.exposed_qk = None
 
     def forward(self, x, mask, cos, sin, attn_mask=None, _runtime=None):
         ops_g3._check_activation(x, "GroupedQueryAttention")
         ops_llama.check_bf16(self, "GroupedQueryAttention")
         B, S, _ = x.shape
         rt = _runtime if _runtime is not None else ops_llama.make_runtime(self, B, S, cos, sin, attn_mask)
-        return ops_llama.GQAFn.apply(x, self, rt, torch.is_grad_enabled(), *ops_llama._param_list(self))
+        return ops_llama.run_attention(self, x, rt)

@@ -9,6 +9,9 @@ Block forward (x [M, d]):
     h1 = rmsnorm(x) -> qkv = h1 [Wq | Wk | Wv]^T -> (q, k) = RoPE(qkv) -> ctx = causal attention (key mask) -> x2 = ctx Wo^T + b + x
     h2 = rmsnorm(x2) -> gu = h2 [W1 | Wg]^T -> a = SwiGLU(gu) -> x3 = a W2^T + x2
 With ``att.track_max_attn_logit`` the per-head maximum attention logit of the post-RoPE q, k is left in ``att.max_attn_logit`` (one more launch).
+With ``att.expose_qk`` and grad mode on, the block's (and the attention's) autograd node returns the post-RoPE q, k as two more differentiable
+outputs, left in ``att.exposed_qk`` (what ``common/reinforced_attention_learning.py`` reads); the gradients that arrive on them are added to dq, dk
+ahead of the RoPE backward.  With the flag off the node has one output and launches what it launched before the flag existed.
 """
 
 import torch
@@ -17,6 +20,7 @@ from . import _lib as L
 from . import kernels as K
 from . import kernels_g3 as KG
 from . import kernels_llama as KL
+from . import kernels_ral as KR
 from .ops import _flush_wgrads, _wgrad, arena_for
 from .ops import make_runtime as _make_runtime
 from .ops_g3 import _add_vecgrad, _check_activation, _flat, _param_list, rope_tables_f32
@@ -59,8 +63,8 @@ def attention_forward(att, arena, h1, rt, residual=None):
     return ao, (qkv, q, k, ctx, lse)
 
 
-def attention_backward(att, arena, h1, saved, dao, rt, defer=None):
-    """Returns dh1 [M, d_in]; writes the gradients of the four projections and the bias."""
+def attention_backward(att, arena, h1, saved, dao, rt, defer=None, qk_grads=(None, None)):
+    """Returns dh1 [M, d_in]; writes the gradients of the four projections and the bias.  ``qk_grads``: what arrived on the exposed q, k (None = zero)."""
     Hq, Hkv, D = att.num_heads, att.num_kv_groups, att.head_dim
     qkv, q, k, ctx, lse = saved
     v = qkv[:, (Hq + Hkv) * D :]
@@ -70,6 +74,9 @@ def attention_backward(att, arena, h1, saved, dao, rt, defer=None):
     _wgrad(arena, att.out_proj.weight, None, dao, ctx, defer)
     dqkv, dq, dk = torch.empty_like(qkv), torch.empty_like(q), torch.empty_like(k)
     K.attn_bwd(q, k, v, ctx, dctx, lse, rt.B, rt.S, Hq, Hkv, D, dq, dk, dqkv[:, (Hq + Hkv) * D :], key_mask=rt.key_mask, causal=True, scale=att.att_scaling)
+    for d, extra in zip((dq, dk), qk_grads):
+        if extra is not None:
+            KR.add_bf16_(d, extra.reshape(d.shape).contiguous())
     KL.rope_bwd(dq, dk, rt.cos, rt.sin, rt.pos, dqkv, Hq, Hkv, D)
     dh1 = K.dgrad(dqkv, arena.fused(att.w_queries.weight, att.w_values.weight))
     _wgrad(arena, att.w_queries.weight, att.w_values.weight, dqkv, h1, defer)
@@ -86,13 +93,13 @@ def block_forward(blk, x, rt, keep):
     return x3, ((x, h1, att_saved, x2, h2, ffn_saved) if keep else None)
 
 
-def block_backward(blk, saved, dx3, rt):
+def block_backward(blk, saved, dx3, rt, qk_grads=(None, None)):
     arena = arena_for(blk)
     x, h1, att_saved, x2, h2, ffn_saved = saved
     wg = []  # the four weight-gradient GEMMs run as one grouped launch at the end
     dh2 = ffn_backward(blk.ffn, arena, h2, ffn_saved, dx3, wg)
     dx2 = _norm_bwd(arena, blk.norm_2, x2, dh2, dres=dx3)
-    dh1 = attention_backward(blk.att, arena, h1, att_saved, dx2, rt, wg)
+    dh1 = attention_backward(blk.att, arena, h1, att_saved, dx2, rt, wg, qk_grads)
     dx = _norm_bwd(arena, blk.norm_1, x, dh1, dres=dx2)
     _flush_wgrads(wg)
     hook = getattr(blk, "_grad_ready", None)
@@ -101,19 +108,43 @@ def block_backward(blk, saved, dx3, rt):
     return dx
 
 
+def _exposes(att, keep):
+    return bool(keep and getattr(att, "expose_qk", False))
+
+
+def _with_exposed(ctx, y, att_saved, expose):
+    """The node's outputs: y, and with ``expose`` the post-RoPE q, k of ``attention_forward``'s saved tuple (aliases: the saved tensors stay plain)."""
+    ctx.exposed = expose
+    if not expose:
+        return y
+    ctx.set_materialize_grads(False)  # a gradient that never arrived stays None and costs no launch
+    return y, att_saved[1].detach(), att_saved[2].detach()
+
+
+def _leave_exposed(att, out):
+    """y of a node's outputs; q, k (if the node returned them) go to ``att.exposed_qk``."""
+    if isinstance(out, tuple):
+        att.exposed_qk = (out[1], out[2])
+        return out[0]
+    att.exposed_qk = None
+    return out
+
+
 class LlamaBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, blk, rt, keep, *params):
         B, S, d = x.shape
         y, saved = block_forward(blk, _flat(x), rt, keep)
         ctx.blk, ctx.rt, ctx.saved, ctx.shape = blk, rt, saved, (B, S, d)
-        return y.view(B, S, d)
+        return _with_exposed(ctx, y.view(B, S, d), saved[2] if keep else None, _exposes(blk.att, keep))
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, *dqk):
         if ctx.saved is None:
             raise RuntimeError("LlamaBlockFn: backward through a forward that ran without grad mode")
-        dx = block_backward(ctx.blk, ctx.saved, _flat(dy), ctx.rt)
+        if dy is None:  # only with exposed q, k: nothing but they reached the loss
+            dy = torch.zeros(ctx.shape, dtype=BF16, device=ctx.saved[0].device)
+        dx = block_backward(ctx.blk, ctx.saved, _flat(dy), ctx.rt, dqk if ctx.exposed else (None, None))
         ctx.saved = None
         return (dx.view(ctx.shape), None, None, None) + (None,) * len(ctx.blk._param_list)
 
@@ -121,7 +152,7 @@ class LlamaBlockFn(torch.autograd.Function):
 def run_block(blk, x, rt):
     _check_activation(x, "Llama TransformerBlock")
     check_bf16(blk, "Llama TransformerBlock")
-    return LlamaBlockFn.apply(x, blk, rt, torch.is_grad_enabled(), *_param_list(blk))
+    return _leave_exposed(blk.att, LlamaBlockFn.apply(x, blk, rt, torch.is_grad_enabled(), *_param_list(blk)))
 
 
 class GQAFn(torch.autograd.Function):
@@ -133,15 +164,22 @@ class GQAFn(torch.autograd.Function):
         x2 = _flat(x)
         ao, saved = attention_forward(att, arena, x2, rt)
         ctx.att, ctx.rt, ctx.shape, ctx.saved = att, rt, x.shape, (x2, saved) if keep else None
-        return ao.view(*x.shape[:-1], ao.shape[1])
+        ctx.oshape = (*x.shape[:-1], ao.shape[1])
+        return _with_exposed(ctx, ao.view(ctx.oshape), saved, _exposes(att, keep))
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, *dqk):
         if ctx.saved is None:
             raise RuntimeError("GroupedQueryAttention: backward through a forward that ran without grad mode")
         x2, saved = ctx.saved
+        if dy is None:
+            dy = torch.zeros(ctx.oshape, dtype=BF16, device=x2.device)
         wg = []
-        dx = attention_backward(ctx.att, arena_for(ctx.att), x2, saved, _flat(dy), ctx.rt, wg)
+        dx = attention_backward(ctx.att, arena_for(ctx.att), x2, saved, _flat(dy), ctx.rt, wg, dqk if ctx.exposed else (None, None))
         _flush_wgrads(wg)
         ctx.saved = None
         return (dx.view(ctx.shape), None, None, None) + (None,) * len(ctx.att._param_list)
+
+
+def run_attention(att, x, rt):
+    return _leave_exposed(att, GQAFn.apply(x, att, rt, torch.is_grad_enabled(), *_param_list(att)))
